@@ -88,6 +88,29 @@ def host_cores():
     return n
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, films, counts):
+    """--dump-outputs: writes what the last timed step computed as out_dir/<name>.npy, so that two builds can be compared
+    output for output.  films: name -> (H, W, 3) array, written as float32; counts: name -> value, written as a float64
+    scalar.  When the films exceed DUMP_LIMIT_BYTES together, every film is reduced to the same seeded sample of pixels,
+    (n, 3), and their film row-major indices go to film_sample_index.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    films = {k: np.asarray(v, dtype=np.float32) for k, v in films.items()}
+    H, W, _ = next(iter(films.values())).shape
+    if sum(a.nbytes for a in films.values()) > DUMP_LIMIT_BYTES:
+        n = (DUMP_LIMIT_BYTES - (1 << 20)) // (12 * len(films) + 8)
+        idx = np.sort(np.random.default_rng(0).choice(H * W, size=n, replace=False))
+        films = {k: a.reshape(H * W, 3)[idx] for k, a in films.items()}
+        np.save(os.path.join(out_dir, "film_sample_index.npy"), idx.astype(np.float64))
+    for k, a in films.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
+    for k, v in counts.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), np.float64(v))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -103,12 +126,17 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--megakernel", action="store_true", help="time the persistent-lanes megakernel instead of the wavefront pipeline")
     ap.add_argument("--film-out", default="", help="rank 0 writes the gathered fp32 film of the last step to this .npy file (tests)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes the outputs of the last timed step to DIR/<name>.npy: film_linear (fp32 film), film_u8 (the "
+                         "tonemapped bytes, as float32), segments_per_step and samples_per_step (float64); at most 64 MB in all")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL; 'gloo' only to rehearse N > 1 "
                     "with all ranks sharing one GPU, where RCCL refuses duplicate devices)")
     ap.add_argument("--force-dist", action="store_true", help="with one rank too: init_process_group(backend) + the all_gather of the film tiles "
                     "(so that the RCCL path has run on a one-GPU box before a multi-GPU node sees it)")
     ap.add_argument("--no-cli-wall-clock", action="store_true", help="skip the one run of the CLI binary behind config.cli_wall_clock_s")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         launch_ranks(args.gpus, sys.argv[1:])      # does not return
@@ -218,6 +246,9 @@ def main():
     kernel_ms = float(kern_max.item())
 
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"film_linear": film_lin.cpu().numpy(), "film_u8": film_u8.cpu().numpy()},
+                         {"segments_per_step": total_rays / args.steps, "samples_per_step": total_samples / args.steps})
         ms_per_step = seconds / args.steps * 1e3
         mrays = total_rays / seconds / 1e6
         # roofline of the dominant kernel on rank 0's device.

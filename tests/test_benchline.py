@@ -112,3 +112,31 @@ def test_bench_gpus_n_without_a_launcher_starts_its_own_ranks_and_relays_failure
     assert p.returncode != 0
     assert "bench.py needs a GPU" in p.stderr, p.stderr[-2000:]
     assert p.stdout.strip() == ""
+
+
+def test_bench_dump_outputs_full_and_sampled(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every film as float32 and every count as a float64 scalar; above the size limit the films are
+    reduced to one seeded sample of pixels, the same for every film and every run, whose indices are written beside them."""
+    import numpy as np
+    import bench
+    r = np.random.default_rng(3)
+    lin = r.random((300, 200, 3), dtype=np.float32)
+    u8 = (lin * 255).astype(np.uint8)
+    bench.dump_outputs(str(tmp_path / "full"), {"film_linear": lin, "film_u8": u8}, {"segments_per_step": 12345.0})
+    got = {f[:-4]: np.load(tmp_path / "full" / f) for f in os.listdir(tmp_path / "full")}
+    assert sorted(got) == ["film_linear", "film_u8", "segments_per_step"]
+    assert got["film_linear"].dtype == np.float32 and np.array_equal(got["film_linear"], lin)
+    assert got["film_u8"].dtype == np.float32 and np.array_equal(got["film_u8"], u8)
+    assert got["segments_per_step"].dtype == np.float64 and got["segments_per_step"] == 12345.0
+
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", (1 << 20) + 32 * 1000)     # the films (1.4 MB) no longer fit
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), {"film_linear": lin, "film_u8": u8}, {})
+    a = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert sorted(a) == ["film_linear", "film_sample_index", "film_u8"]
+    assert sum(x.nbytes for x in a.values()) <= bench.DUMP_LIMIT_BYTES
+    idx = a["film_sample_index"].astype(np.int64)
+    assert len(idx) == 1000 and len(np.unique(idx)) == 1000 and np.array_equal(a["film_sample_index"], idx)
+    assert np.array_equal(a["film_linear"], lin.reshape(-1, 3)[idx]) and np.array_equal(a["film_u8"], u8.reshape(-1, 3)[idx])
+    for k, v in a.items():
+        assert np.array_equal(np.load(tmp_path / "b" / f"{k}.npy"), v)

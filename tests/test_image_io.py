@@ -2,9 +2,11 @@
 against the reference's own vendored stb (dependencies/stb, compiled from where it lies into
 oracle/_ref/libstbref.so by oracle/Makefile; SURVEY.md §8c "partial oracle that does build") and against
 golden bytes committed under tests/golden/ (generated with that stb by tests/golden/make_io_fixtures.py),
-so the GPU box — which has no /root/reference — still checks them."""
+so a checkout without the reference tree still checks them."""
 import ctypes as C
 import os
+import struct
+import zlib
 
 import numpy as np
 import pytest
@@ -50,15 +52,61 @@ def test_hdr_roundtrip_own_codec(built, tmp_path):
         assert np.array_equal(api.read_hdr(p2), back)             # RGBE values are a fixed point
 
 
+def _decode_png_rgb8(raw):
+    """A PNG decoder independent of the product's and of stb: 8-bit RGB, not interlaced, CRCs checked, filters 0-4
+    undone as the PNG specification (section 9) defines them."""
+    assert raw[:8] == b"\x89PNG\r\n\x1a\n"
+    p, idat, ihdr = 8, b"", None
+    while p < len(raw):
+        n, kind = struct.unpack(">I4s", raw[p:p + 8])
+        data = raw[p + 8:p + 8 + n]
+        assert struct.unpack(">I", raw[p + 8 + n:p + 12 + n])[0] == zlib.crc32(kind + data), kind
+        if kind == b"IHDR":
+            ihdr = struct.unpack(">IIBBBBB", data)
+        elif kind == b"IDAT":
+            idat += data
+        p += 12 + n
+    w, h, depth, ctype, _, _, interlace = ihdr
+    assert (depth, ctype, interlace) == (8, 2, 0)
+    rows = np.frombuffer(zlib.decompress(idat), np.uint8).reshape(h, 1 + 3 * w)
+    out = np.zeros((h, 3 * w), np.int32)
+    for j in range(h):
+        ft, x = rows[j, 0], rows[j, 1:].astype(np.int32)
+        up = out[j - 1] if j else np.zeros(3 * w, np.int32)
+        if ft in (0, 2):
+            out[j] = (x + (up if ft == 2 else 0)) & 255
+            continue
+        assert ft in (1, 3, 4), ft
+        for i in range(3 * w):
+            a = out[j, i - 3] if i >= 3 else 0
+            c = up[i - 3] if i >= 3 else 0
+            if ft == 1:
+                pred = a
+            elif ft == 3:
+                pred = (a + up[i]) // 2
+            else:
+                pa, pb, pc = abs(up[i] - c), abs(a - c), abs(a + up[i] - 2 * c)
+                pred = a if pa <= pb and pa <= pc else (up[i] if pb <= pc else c)
+            out[j, i] = (x[i] + pred) & 255
+    return out.astype(np.uint8).reshape(h, w, 3)
+
+
 def test_hdr_reader_matches_reference_stb(built, tmp_path):
-    """stbi_loadf (texture.cpp:101) on files written by our writer AND by stb's writer."""
-    stb = _stb()
-    if stb is None:
-        pytest.skip("oracle/_ref/libstbref.so not built (reference tree absent): covered by the golden file test")
+    """stbi_loadf (texture.cpp:101) on files written by our writer AND by stb's writer.  stb's file of the test image and what
+    stb decodes from both files are stored in tests/golden/io_stb_checks.npz (make_io_fixtures.py); when
+    oracle/_ref/libstbref.so is built, the same comparisons run against the live stb too."""
     from hobbyraytracer_amd import api
+    gold = np.load(os.path.join(GOLD, "io_stb_checks.npz"))
     img = _test_image()
+    assert np.array_equal(gold["hdr_image"].view(np.uint32), img.view(np.uint32))
     ours, theirs = str(tmp_path / "ours.hdr"), str(tmp_path / "theirs.hdr")
     api.write_hdr(ours, img)
+    gold["hdr_stb_written"].tofile(theirs)
+    for path, key in ((ours, "hdr_ours_decoded_by_stb"), (theirs, "hdr_stb_written_decoded_by_stb")):
+        assert np.array_equal(api.read_hdr(path).view(np.uint32), gold[key].view(np.uint32)), path
+    stb = _stb()
+    if stb is None:
+        return
     assert stb.stbi_write_hdr(theirs.encode(), img.shape[1], img.shape[0], 3, img.ctypes.data_as(C.POINTER(C.c_float))) == 1
     for path in (ours, theirs):
         w, h, ch = C.c_int(), C.c_int(), C.c_int()
@@ -69,23 +117,31 @@ def test_hdr_reader_matches_reference_stb(built, tmp_path):
 
 
 def test_png_writer_decodes_identically_with_reference_stb(built, tmp_path):
-    """Film::outputFilm's PNG (film.cpp:63): our file decoded by stb == pixels; stb's file decoded by us == pixels."""
+    """Film::outputFilm's PNG (film.cpp:63): our file decoded by stb == pixels; stb's file decoded by us == pixels.  stb's file
+    is stored in tests/golden/io_stb_checks.npz (make_io_fixtures.py, which also checked stb's decoding of our file); our file
+    is decoded by a decoder of the PNG specification's own, and by the live stb when oracle/_ref/libstbref.so is built."""
     from hobbyraytracer_amd import api
+    gold = np.load(os.path.join(GOLD, "io_stb_checks.npz"))
     r = np.random.default_rng(4)
     img = r.integers(0, 256, (37, 53, 3), dtype=np.uint8)
+    assert np.array_equal(gold["png_image"], img)
     ours = str(tmp_path / "ours.png")
     api.write_image(ours, img)
     assert np.array_equal(api.read_png(ours), img)
+    assert np.array_equal(_decode_png_rgb8(open(ours, "rb").read()), img)
+    theirs = str(tmp_path / "theirs.png")
+    gold["png_stb_written"].tofile(theirs)
+    assert np.array_equal(_decode_png_rgb8(open(theirs, "rb").read()), img)
+    assert np.array_equal(api.read_png(theirs), img)             # stb uses filters 0-4 per row: exercises the unfilter code
     stb = _stb()
     if stb is None:
-        pytest.skip("oracle/_ref/libstbref.so not built")
+        return
     w, h, ch = C.c_int(), C.c_int(), C.c_int()
     ptr = stb.stbi_load(ours.encode(), C.byref(w), C.byref(h), C.byref(ch), 3)
     assert ptr and (w.value, h.value) == (53, 37)
     assert np.array_equal(np.ctypeslib.as_array(ptr, shape=(37, 53, 3)), img)
-    theirs = str(tmp_path / "theirs.png")
     assert stb.stbi_write_png(theirs.encode(), 53, 37, 3, img.ctypes.data, 53 * 3) == 1
-    assert np.array_equal(api.read_png(theirs), img)             # stb uses filters 0-4 per row: exercises the unfilter code
+    assert np.array_equal(api.read_png(theirs), img)
 
 
 def test_golden_files_written_by_reference_stb(built):
