@@ -114,6 +114,11 @@ class Stats(C.Structure):
         return 32 * self.box_tests + 36 * self.tri_tests + 60 * self.mesh_hits + 12 * self.env_lookups + 12 * n_pixels
 
 
+class Adaptive(C.Structure):
+    """hrt_adaptive: the schedule and stopping rule of an adaptive render (include/hrt.h)."""
+    _fields_ = [("min_samples", C.c_int32), ("pass_samples", C.c_int32), ("threshold", C.c_float), ("floor", C.c_float)]
+
+
 class Hit(C.Structure):
     _fields_ = [("t", C.c_float), ("prim", C.c_int32), ("tri", C.c_int32), ("front_face", C.c_int32), ("p", C.c_float * 3),
                 ("normal", C.c_float * 3), ("u", C.c_float), ("v", C.c_float)]
@@ -127,7 +132,8 @@ HIP_SYMBOLS = ["hrt_device_count", "hrt_scene_create", "hrt_scene_destroy", "hrt
                "hrt_render_stripes", "hrt_render_stripes_accumulate_device", "hrt_render_stripes_accumulate", "hrt_stripe_rows", "hrt_stripe_row_index", "hrt_scene_stats", "hrt_resolve_u8",
                "hrt_resolve_u8_device", "hrt_closest_hit", "hrt_math_probe", "hrt_status_str", "hrt_last_error", "hrt_version",
                "hrt_multi_create", "hrt_multi_destroy", "hrt_multi_devices", "hrt_multi_uses_rccl", "hrt_multi_render", "hrt_bvh_build_device", "hrt_bvh_build_sah",
-               "hrt_debug_bounds_violations", "hrt_scene_progress", "hrt_multi_progress"]
+               "hrt_debug_bounds_violations", "hrt_scene_progress", "hrt_multi_progress",
+               "hrt_render_stripes_adaptive_device", "hrt_render_stripes_adaptive", "hrt_adaptive_mean_device"]
 HOST_SYMBOLS = ["hrt_host_load_yaml", "hrt_host_free", "hrt_host_flat", "hrt_host_film", "hrt_host_camera", "hrt_host_bvh_depth",
                 "hrt_default_params", "hrt_asset_write_teapot_obj", "hrt_asset_write_bust_obj", "hrt_asset_write_hall_hdr",
                 "hrt_host_write_image", "hrt_host_read_hdr", "hrt_host_read_png", "hrt_host_read_jpeg", "hrt_host_write_hdr", "hrt_host_write_pfm", "hrt_host_read_pfm", "hrt_host_last_error", "hrt_host_set_bvh_builder"]
@@ -161,6 +167,12 @@ _hip.hrt_render_stripes_accumulate_device.argtypes = [_vp, C.POINTER(Camera), C.
                                                       C.c_int32, C.c_int32, _vp]
 _hip.hrt_render_stripes_accumulate.argtypes = [_vp, C.POINTER(Camera), C.POINTER(Params), C.c_int32, C.c_int32, C.c_int32, _fp,
                                                C.c_int32, C.c_int32, C.POINTER(Stats)]
+_hip.hrt_render_stripes_adaptive_device.argtypes = [_vp, C.POINTER(Camera), C.POINTER(Params), C.c_int32, C.c_int32, C.c_int32,
+                                                   C.POINTER(Adaptive), _vp, _vp, _vp, C.c_int32, C.POINTER(C.c_int64), _vp]
+_hip.hrt_render_stripes_adaptive.argtypes = [_vp, C.POINTER(Camera), C.POINTER(Params), C.c_int32, C.c_int32, C.c_int32,
+                                            C.POINTER(Adaptive), _fp, _fp, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int64),
+                                            C.POINTER(Stats)]
+_hip.hrt_adaptive_mean_device.argtypes = [_vp, _vp, _vp, C.c_int64, _vp, _vp]
 _hip.hrt_stripe_rows.argtypes = [C.c_int32] * 4
 _hip.hrt_stripe_rows.restype = C.c_int32
 _hip.hrt_stripe_row_index.argtypes = [C.c_int32] * 5
@@ -461,6 +473,62 @@ class DeviceScene:
     def render_stripes_accumulate_device(self, cam, params, rows_per_block, rank, n_ranks, d_accum_ptr, sample_first, sample_count, stream=0):
         _check(_hip.hrt_render_stripes_accumulate_device(self._h, C.byref(cam), C.byref(params), rows_per_block, rank, n_ranks,
                                                          _vp(d_accum_ptr), sample_first, sample_count, _vp(stream)))
+
+    def render_stripes_adaptive(self, cam, params, rows_per_block, rank, n_ranks, adaptive, pass_index, sums=None, sq=None, count=None):
+        """One adaptive pass (hrt_render_stripes_adaptive) -> (sums, sq, count, active, Stats).  Pass 0 allocates the buffers when
+        they are not given (rows x W x 3 float32, rows x W float32, rows x W int32, stripe layout); later passes continue the ones
+        returned.  active = pixels rendered in this pass (0: the render is finished)."""
+        rows = stripe_rows(params.height, rows_per_block, rank, n_ranks)
+        if sums is None:
+            sums = np.empty((rows, params.width, 3), dtype=np.float32)
+        if sq is None:
+            sq = np.empty((rows, params.width), dtype=np.float32)
+        if count is None:
+            count = np.zeros((rows, params.width), dtype=np.int32)
+        for a, dt, n in ((sums, np.float32, rows * params.width * 3), (sq, np.float32, rows * params.width), (count, np.int32, rows * params.width)):
+            assert a.dtype == dt and a.flags["C_CONTIGUOUS"] and a.size == n
+        if not isinstance(adaptive, Adaptive):
+            adaptive = Adaptive(*adaptive)
+        active = C.c_int64(0)
+        st = Stats()
+        _check(_hip.hrt_render_stripes_adaptive(self._h, C.byref(cam), C.byref(params), rows_per_block, rank, n_ranks, C.byref(adaptive),
+                                                _ptr(sums), _ptr(sq), _ptr(count, C.POINTER(C.c_int32)), pass_index, C.byref(active),
+                                                C.byref(st)))
+        return sums, sq, count, active.value, st
+
+    def render_stripes_adaptive_device(self, cam, params, rows_per_block, rank, n_ranks, adaptive, d_sums_ptr, d_sq_ptr, d_count_ptr,
+                                       pass_index, stream=0):
+        """Device-buffer pass (hrt_render_stripes_adaptive_device) -> active pixels of the pass."""
+        if not isinstance(adaptive, Adaptive):
+            adaptive = Adaptive(*adaptive)
+        active = C.c_int64(0)
+        _check(_hip.hrt_render_stripes_adaptive_device(self._h, C.byref(cam), C.byref(params), rows_per_block, rank, n_ranks,
+                                                       C.byref(adaptive), _vp(d_sums_ptr), _vp(d_sq_ptr), _vp(d_count_ptr), pass_index,
+                                                       C.byref(active), _vp(stream)))
+        return active.value
+
+    def adaptive_mean_device(self, d_sums_ptr, d_count_ptr, n_pixels, d_mean_ptr, stream=0):
+        _check(_hip.hrt_adaptive_mean_device(self._h, _vp(d_sums_ptr), _vp(d_count_ptr), n_pixels, _vp(d_mean_ptr), _vp(stream)))
+
+    def render_adaptive(self, cam, params, adaptive, rows_per_block=8, rank=0, n_ranks=1, on_pass=None):
+        """Runs adaptive passes until none is active -> (mean, count, Stats summed over the passes).  mean = sums / count
+        (rows x W x 3 float32, stripe layout; the film itself for n_ranks == 1).  on_pass(pass_index, sums, count, active)
+        is called after every pass that rendered."""
+        sums = sq = count = None
+        total = Stats()
+        p = 0
+        while True:
+            sums, sq, count, active, st = self.render_stripes_adaptive(cam, params, rows_per_block, rank, n_ranks, adaptive, p, sums, sq, count)
+            for name, _ in Stats._fields_:
+                setattr(total, name, getattr(total, name) + getattr(st, name))
+            if active == 0:
+                break
+            if on_pass is not None:
+                on_pass(p, sums, count, active)
+            p += 1
+        with np.errstate(divide="ignore", invalid="ignore"):
+            mean = sums / count.astype(np.float32)[..., None]
+        return mean, count, total
 
     def stats(self):
         st = Stats()

@@ -12,6 +12,7 @@
 //   k_resolve           Film::tonemap + Film::writeColour (film.cpp:25-52).
 //   k_closest_hit       world->hit() for test rays (parity tests).
 //   k_math_probe        the shared math kernels, for CPU==GPU bit tests.
+//   k_ad_select / k_ad_scan / k_wf_reduce_list / k_ad_mean   adaptive sampling.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>   // types and prototypes only: the library is loaded on demand (rccl_api below)
 #include <dlfcn.h>
@@ -35,7 +36,7 @@ using namespace hrt;
 namespace {
 
 struct RenderMap {
-    int32_t mode;            // 0 = rect tile, 1 = interleaved row blocks
+    int32_t mode;            // 0 = rect tile, 1 = interleaved row blocks, 2 = list of row-block pixels (adaptive passes)
     int32_t x0, y0;          // rect origin
     int32_t rw, rh;          // local region size
     int32_t R, rank, G;      // stripes
@@ -44,7 +45,13 @@ struct RenderMap {
     // exact division of 32-bit numbers by rw and by rw*rh as multiply-high + shift (host-computed magic
     // numbers, fastdiv below): the wavefront kernels turn slot ids into (sample, pixel) for every path
     uint64_t m_rw, m_nl;
+    // mode 2: local pixel lp of the batch is pixel pix[lp] of the row-block layout (an index in [0, rw * rh), the stripe
+    // order of mode 1); n_list entries, every one of them at the same sample count
+    const int32_t* pix;
+    uint32_t n_list;
 };
+// pixels one render call of `map` covers
+inline uint32_t map_pixels(const RenderMap& map) { return map.mode == 2 ? map.n_list : (uint32_t)map.rw * (uint32_t)map.rh; }
 
 // floor(x / d) for any 32-bit x: with m = floor(2^64 / d) + 1 the product's high half is exact for every
 // x < 2^32 (the error term x / 2^64 * d stays below 1 / d).  d = 1 needs no magic.
@@ -347,6 +354,7 @@ struct WfScene {                 // world-list split points (host-computed)
 };
 
 __device__ inline void slot_pixel(const RenderMap& map, unsigned lp, int& px, int& py) {
+    if (map.mode == 2) lp = (unsigned)map.pix[lp];   // (uniform branch) the list holds indices of the mode-1 layout
     const int ly = (int)fastdiv(lp, (unsigned)map.rw, map.m_rw);
     const int lx = (int)(lp - (unsigned)ly * (unsigned)map.rw);
     if (map.mode == 0) { px = map.x0 + lx; py = map.y0 + ly; }
@@ -1252,6 +1260,124 @@ __global__ __launch_bounds__(256) void k_preview_mean(const float* __restrict__ 
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) mean[i] = sums[i] / samples_done;
 }
 
+
+// ---- adaptive sampling (hrt_render_stripes_adaptive*): per-pixel sums, sums of squared luminance and sample counts, in the
+// ---- row-block layout of mode 1; the passes render the compacted list of the pixels still active (RenderMap mode 2)
+
+// Luminance of one radiance (-ffp-contract=off: three products, added left to right; tests restate it in float32).
+__device__ inline float ad_luma(float r, float g, float b) { return 0.2126f * r + 0.7152f * g + 0.0722f * b; }
+
+// k_wf_reduce for a list batch: per list entry, the batch's samples IN SAMPLE ORDER into the pixel's sums and, as Y*Y, into
+// its sq; count = the samples summed so far.  Never divides (hrt_adaptive_mean_device does).
+__global__ __launch_bounds__(256) void k_wf_reduce_list(const float4* __restrict__ rad, const int32_t* __restrict__ pix, unsigned n_list,
+                                                        int chunk, int first_chunk, int n_after, float* __restrict__ sums,
+                                                        float* __restrict__ sq, int32_t* __restrict__ count, DeviceCounters* counters,
+                                                        unsigned long long* __restrict__ wave_rays, unsigned n_wave_rays) {
+    const unsigned stride = gridDim.x * blockDim.x;
+    for (unsigned lp = blockIdx.x * blockDim.x + threadIdx.x; lp < n_list; lp += stride) {
+        const size_t q = (size_t)(unsigned)pix[lp];
+        vec3 sum(0.0f);
+        float y2 = 0.0f;
+        if (!first_chunk) { sum = vec3(sums[3 * q], sums[3 * q + 1], sums[3 * q + 2]); y2 = sq[q]; }
+        for (int s = 0; s < chunk; ++s) {
+            const float4 r = rad[(size_t)s * n_list + lp];
+            sum += vec3(r.x, r.y, r.z);
+            const float y = ad_luma(r.x, r.y, r.z);
+            y2 += y * y;
+        }
+        sums[3 * q] = sum.x; sums[3 * q + 1] = sum.y; sums[3 * q + 2] = sum.z;
+        sq[q] = y2;
+        count[q] = n_after;
+    }
+    if (blockIdx.x == 0) {   // the batch's segment and sample counts, as k_wf_reduce folds them
+        __shared__ unsigned long long total;
+        if (threadIdx.x == 0) total = 0;
+        __syncthreads();
+        unsigned long long mine = 0;
+        for (unsigned i = threadIdx.x; i < n_wave_rays; i += blockDim.x) { mine += wave_rays[i]; wave_rays[i] = 0; }
+        if (mine) atomicAdd(&total, mine);
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            if (total) atomicAdd(&counters->rays, total);
+            atomicAdd(&counters->samples, (unsigned long long)n_list * (unsigned long long)chunk);
+        }
+    }
+}
+
+struct AdRule {
+    int first;            // pass 0: every pixel is active, the buffers are not read
+    int n;                // the sample count of the pixels still active
+    int min_samples;
+    float threshold, floor;
+};
+// Whether pixel q takes part in the next pass (hrt.h: the stopping rule).  Written so that a NaN anywhere keeps the pixel going.
+__device__ inline bool ad_active(const AdRule& a, const float* __restrict__ sums, const float* __restrict__ sq,
+                                 const int32_t* __restrict__ count, size_t q) {
+    if (a.first) return true;
+    if (count[q] != a.n) return false;                    // stopped in an earlier pass
+    const float n = (float)a.n;
+    const float m = ad_luma(sums[3 * q], sums[3 * q + 1], sums[3 * q + 2]) / n;
+    float var = (sq[q] - n * m * m) / (n - 1.0f);
+    if (var < 0.0f) var = 0.0f;                           // (not fmaxf: a NaN must stay NaN)
+    const float e = a.threshold * (m > a.floor ? m : a.floor);
+    return !(a.n >= a.min_samples && var / n < e * e);
+}
+
+// Compaction of the active pixels into the list, in ascending order: block b owns pixels [b * AD_ITEMS, (b + 1) * AD_ITEMS),
+// WRITE = 0 counts them (blocks[b]), WRITE = 1 writes them from offset blocks[b] on (the exclusive scan of the counts).
+#define AD_ITEMS 1024
+template <int WRITE>
+__global__ __launch_bounds__(256) void k_ad_select(AdRule a, const float* __restrict__ sums, const float* __restrict__ sq,
+                                                   const int32_t* __restrict__ count, unsigned n_local, unsigned* __restrict__ blocks,
+                                                   int32_t* __restrict__ pix) {
+    __shared__ unsigned wave_n[4];
+    const unsigned lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    unsigned carry = WRITE ? blocks[blockIdx.x] : 0u;
+    const unsigned b0 = blockIdx.x * AD_ITEMS;
+    for (unsigned k = 0; k < AD_ITEMS; k += 256) {
+        const unsigned q = b0 + k + threadIdx.x;
+        const bool act = q < n_local && ad_active(a, sums, sq, count, q);
+        const unsigned long long m = __ballot(act);
+        if (lane == 0) wave_n[wv] = (unsigned)__popcll(m);
+        __syncthreads();
+        unsigned before = 0, all = 0;
+        for (unsigned v = 0; v < 4; ++v) { const unsigned c = wave_n[v]; before += v < wv ? c : 0u; all += c; }
+        if (WRITE && act) pix[carry + before + lanes_below(m)] = (int32_t)q;
+        carry += all;
+        __syncthreads();
+    }
+    if (!WRITE && threadIdx.x == 0) blocks[blockIdx.x] = carry;
+}
+// Exclusive scan of the n block counts in place (one block); blocks[n] = the total.
+__global__ __launch_bounds__(256) void k_ad_scan(unsigned* __restrict__ blocks, unsigned n) {
+    __shared__ unsigned part[256];
+    unsigned carry = 0;
+    for (unsigned i0 = 0; i0 < n; i0 += 256) {
+        const unsigned i = i0 + threadIdx.x;
+        const unsigned v = i < n ? blocks[i] : 0u;
+        part[threadIdx.x] = v;
+        __syncthreads();
+        for (unsigned off = 1; off < 256; off <<= 1) {   // Hillis-Steele inclusive scan
+            const unsigned t = threadIdx.x >= off ? part[threadIdx.x - off] : 0u;
+            __syncthreads();
+            part[threadIdx.x] += t;
+            __syncthreads();
+        }
+        if (i < n) blocks[i] = carry + part[threadIdx.x] - v;
+        carry += part[255];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) blocks[n] = carry;
+}
+// mean = sums / count per pixel (the division of k_wf_reduce: count == samples gives the bits of the uniform render).
+__global__ __launch_bounds__(256) void k_ad_mean(const float* __restrict__ sums, const int32_t* __restrict__ count, long long n,
+                                                 float* __restrict__ mean) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const float c = static_cast<float>(count[i]);
+        mean[3 * i] = sums[3 * i] / c; mean[3 * i + 1] = sums[3 * i + 1] / c; mean[3 * i + 2] = sums[3 * i + 2] / c;
+    }
+}
+
 }  // namespace
 
 // ===================================================================== host side of the ABI
@@ -1318,6 +1444,10 @@ struct hrt_scene {
     unsigned long long* d_progress = nullptr;
     unsigned long long progress_base = 0;
     volatile unsigned long long progress_total = 0;
+    // adaptive passes: the list of active pixels (ad_cap entries) and the block counts of its compaction (+ the total)
+    int32_t* d_ad_pix = nullptr;
+    unsigned* d_ad_blocks = nullptr;
+    size_t ad_cap = 0;
 };
 
 namespace {
@@ -1557,9 +1687,10 @@ hrt_status wf_reserve(hrt_scene* sc, size_t slots, int depth) {
 // render() as the wavefront pipeline: see the comment above struct WfBuf.
 // Samples [s_first, s_first + s_count) of pr->samples are added, in sample order, to the sums held in d_out
 // (s_first == 0 starts them); the batch that reaches pr->samples divides (main.cpp:126).
+// List maps (mode 2, adaptive passes) add the samples to d_out = sums, d_sq and d_count instead (k_wf_reduce_list: no division).
 hrt_status launch_wavefront(hrt_scene* sc, const hrt_camera* cam, const hrt_params* pr, const RenderMap& map, float* d_out,
-                            hipStream_t stream, int s_first, int s_count) {
-    const unsigned n_local = (unsigned)map.rw * (unsigned)map.rh;
+                            hipStream_t stream, int s_first, int s_count, float* d_sq, int32_t* d_count) {
+    const unsigned n_local = map_pixels(map);
     const int D = pr->max_depth;
     const int n_mesh = (int)sc->mesh_prims.size();
     size_t cap = wf_max_slots(sc);
@@ -1717,7 +1848,10 @@ hrt_status launch_wavefront(hrt_scene* sc, const hrt_camera* cam, const hrt_para
 #undef HRT_LAUNCH_TAIL
         }
         const int rblocks = (int)std::min<size_t>((n_local + 255) / 256, (size_t)sc->n_cus * 8);
-        hipLaunchKernelGGL(k_wf_reduce, dim3(rblocks), dim3(256), 0, stream, w.rad, n_local, c, s0 == 0 ? 1 : 0, s0 + c >= pr->samples ? 1 : 0, pr->samples, d_out, sc->d_counters, w.wave_rays, w.n_wave_rays);
+        if (map.mode == 2)
+            hipLaunchKernelGGL(k_wf_reduce_list, dim3(rblocks), dim3(256), 0, stream, w.rad, map.pix, n_local, c, s0 == 0 ? 1 : 0, s0 + c, d_out, d_sq, d_count, sc->d_counters, w.wave_rays, w.n_wave_rays);
+        else
+            hipLaunchKernelGGL(k_wf_reduce, dim3(rblocks), dim3(256), 0, stream, w.rad, n_local, c, s0 == 0 ? 1 : 0, s0 + c >= pr->samples ? 1 : 0, pr->samples, d_out, sc->d_counters, w.wave_rays, w.n_wave_rays);
         if (progress) {
             sc->progress_base += n_slots;
             hipLaunchKernelGGL(k_set_progress, dim3(1), dim3(1), 0, stream, sc->progress_base, sc->d_progress);
@@ -1728,7 +1862,7 @@ hrt_status launch_wavefront(hrt_scene* sc, const hrt_camera* cam, const hrt_para
 }
 
 hrt_status launch_pathtrace(hrt_scene* sc, const hrt_camera* cam, const hrt_params* pr, const RenderMap& map, float* d_out,
-                            hipStream_t stream, int s_first = 0, int s_count = -1) {
+                            hipStream_t stream, int s_first = 0, int s_count = -1, float* d_sq = nullptr, int32_t* d_count = nullptr) {
     if (map.total_items <= 0) return HRT_OK;
     if (s_count < 0) s_count = pr->samples - s_first;
     if (s_first < 0 || s_count < 1 || s_first + s_count > pr->samples) return fail(HRT_ERR_INVALID, "sample range outside [0, samples)");
@@ -1738,7 +1872,7 @@ hrt_status launch_pathtrace(hrt_scene* sc, const hrt_camera* cam, const hrt_para
         // (reset in stream order: an earlier asynchronous call's last write may still be on its way)
         hipLaunchKernelGGL(k_set_progress, dim3(1), dim3(1), 0, stream, 0ull, sc->d_progress);
         sc->progress_base = 0;
-        sc->progress_total = (unsigned long long)map.rw * (unsigned long long)map.rh * (unsigned long long)s_count;
+        sc->progress_total = (unsigned long long)map_pixels(map) * (unsigned long long)s_count;
     }
     hipEvent_t a, b;
     hrt_status st = get_event(sc, &a);
@@ -1747,7 +1881,7 @@ hrt_status launch_pathtrace(hrt_scene* sc, const hrt_camera* cam, const hrt_para
     if (st != HRT_OK) return st;
     HIPCHK(hipEventRecord(a, stream));
     st = (pr->flags & HRT_FLAG_MEGAKERNEL) ? launch_megakernel(sc, cam, pr, map, d_out, stream)
-                                           : launch_wavefront(sc, cam, pr, map, d_out, stream, s_first, s_count);
+                                           : launch_wavefront(sc, cam, pr, map, d_out, stream, s_first, s_count, d_sq, d_count);
     if (st != HRT_OK) return st;
     if (pr->flags & HRT_FLAG_PROGRESS) {   // whatever path rendered: everything has ended
         hipLaunchKernelGGL(k_set_progress, dim3(1), dim3(1), 0, stream, (unsigned long long)sc->progress_total, sc->d_progress);
@@ -1844,6 +1978,8 @@ void hrt_scene_destroy(hrt_scene* sc) {
     for (auto& p : sc->pending_trav) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (hipEvent_t e : sc->event_pool) (void)hipEventDestroy(e);
     if (sc->wf.base) (void)hipFree(sc->wf.base);
+    if (sc->d_ad_pix) (void)hipFree(sc->d_ad_pix);
+    if (sc->d_ad_blocks) (void)hipFree(sc->d_ad_blocks);
     for (void* p : sc->allocs) (void)hipFree(p);
     if (sc->h_progress) (void)hipHostFree((void*)sc->h_progress);
     delete sc;
@@ -2036,6 +2172,130 @@ hrt_status hrt_render_stripes_accumulate(hrt_scene* sc, const hrt_camera* cam, c
     st = hrt_scene_stats(sc, &now);
     if (st != HRT_OK) return st;
     if (stats) *stats = now;
+    return HRT_OK;
+    HRT_API_CATCH
+}
+
+namespace {
+hrt_status check_adaptive(hrt_scene* sc, const hrt_camera* cam, const hrt_params* pr, int32_t R, int32_t rank, int32_t G, const hrt_adaptive* ad,
+                          int32_t pass, int64_t* active_out) {
+    if (!sc || !cam || !ad || !active_out) return fail(HRT_ERR_INVALID, "NULL argument");
+    hrt_status st = check_params(pr);
+    if (st != HRT_OK) return st;
+    if (R <= 0 || G <= 0 || rank < 0 || rank >= G) return fail(HRT_ERR_INVALID, "bad stripe partition");
+    if (pr->flags & HRT_FLAG_MEGAKERNEL) return fail(HRT_ERR_UNSUPPORTED, "adaptive sampling renders on the wavefront pipeline only");
+    if (ad->min_samples < 2 || ad->min_samples > pr->samples) return fail(HRT_ERR_INVALID, "min_samples must lie in [2, samples]");
+    if (ad->pass_samples < 1) return fail(HRT_ERR_INVALID, "pass_samples must be >= 1");
+    if (!(ad->threshold >= 0.0f) || !(ad->floor >= 0.0f)) return fail(HRT_ERR_INVALID, "threshold and floor must be >= 0 (and not NaN)");
+    if (pass < 0) return fail(HRT_ERR_INVALID, "pass must be >= 0");
+    return HRT_OK;
+}
+// samples every still-active pixel has before `pass` (all of them share it: a stopped pixel never restarts)
+int64_t adaptive_done(const hrt_params* pr, const hrt_adaptive* ad, int32_t pass) {
+    if (pass == 0) return 0;
+    return std::min<int64_t>(pr->samples, (int64_t)ad->min_samples + (int64_t)(pass - 1) * ad->pass_samples);
+}
+}  // namespace
+
+hrt_status hrt_render_stripes_adaptive_device(hrt_scene* sc, const hrt_camera* cam, const hrt_params* pr, int32_t R, int32_t rank, int32_t G,
+                                              const hrt_adaptive* ad, float* d_sums, float* d_sq, int32_t* d_count, int32_t pass,
+                                              int64_t* active_out, void* stream) {
+    HRT_API_TRY
+    hrt_status st = check_adaptive(sc, cam, pr, R, rank, G, ad, pass, active_out);
+    if (st != HRT_OK) return st;
+    if (!d_sums || !d_sq || !d_count) return fail(HRT_ERR_INVALID, "NULL argument");
+    *active_out = 0;
+    const int64_t done = adaptive_done(pr, ad, pass);
+    const int32_t rows = hrt_stripe_rows(pr->height, R, rank, G);
+    const uint32_t n_local = (uint32_t)pr->width * (uint32_t)rows;
+    if (n_local == 0 || done >= pr->samples) return HRT_OK;
+    const int n_samples = pass == 0 ? ad->min_samples : (int)std::min<int64_t>(ad->pass_samples, pr->samples - done);
+    HIPCHK(hipSetDevice(sc->device));
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned n_blocks = (n_local + AD_ITEMS - 1) / AD_ITEMS;
+    if (sc->ad_cap < n_local) {
+        HIPCHK(hipDeviceSynchronize());       // an earlier pass may still read the list
+        if (sc->d_ad_pix) { (void)hipFree(sc->d_ad_pix); sc->d_ad_pix = nullptr; }
+        if (sc->d_ad_blocks) { (void)hipFree(sc->d_ad_blocks); sc->d_ad_blocks = nullptr; }
+        sc->ad_cap = 0;
+        hipError_t e = hipMalloc((void**)&sc->d_ad_pix, (size_t)n_local * sizeof(int32_t));
+        if (e == hipSuccess) e = hipMalloc((void**)&sc->d_ad_blocks, ((size_t)n_blocks + 1) * sizeof(unsigned));
+        if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? HRT_ERR_OOM : HRT_ERR_HIP, std::string("hipMalloc(adaptive list): ") + hipGetErrorString(e));
+        sc->ad_cap = n_local;
+    }
+    AdRule rule{pass == 0 ? 1 : 0, (int)done, ad->min_samples, ad->threshold, ad->floor};
+    hipLaunchKernelGGL(k_ad_select<0>, dim3(n_blocks), dim3(256), 0, s, rule, d_sums, d_sq, d_count, n_local, sc->d_ad_blocks, sc->d_ad_pix);
+    hipLaunchKernelGGL(k_ad_scan, dim3(1), dim3(256), 0, s, sc->d_ad_blocks, n_blocks);
+    hipLaunchKernelGGL(k_ad_select<1>, dim3(n_blocks), dim3(256), 0, s, rule, d_sums, d_sq, d_count, n_local, sc->d_ad_blocks, sc->d_ad_pix);
+    HIPCHK(hipGetLastError());
+    unsigned n_active = 0;                    // the batch size: one 4-byte read-back per pass
+    HIPCHK(hipMemcpyAsync(&n_active, sc->d_ad_blocks + n_blocks, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (n_active > n_local) return fail(HRT_ERR_HIP, "adaptive compaction produced more pixels than the stripes hold");
+    *active_out = n_active;
+    if (n_active == 0) return HRT_OK;
+    RenderMap map{};
+    map.mode = 2; map.R = R; map.rank = rank; map.G = G;
+    map.rw = pr->width; map.rh = rows;
+    map.pix = sc->d_ad_pix; map.n_list = n_active;
+    map.total_items = (int32_t)n_active;
+    map.m_rw = fastdiv_magic((uint32_t)map.rw); map.m_nl = fastdiv_magic(n_active);
+    return launch_pathtrace(sc, cam, pr, map, d_sums, s, (int)done, n_samples, d_sq, d_count);
+    HRT_API_CATCH
+}
+
+hrt_status hrt_render_stripes_adaptive(hrt_scene* sc, const hrt_camera* cam, const hrt_params* pr, int32_t R, int32_t rank, int32_t G,
+                                       const hrt_adaptive* ad, float* sums, float* sq, int32_t* count, int32_t pass, int64_t* active_out,
+                                       hrt_stats* stats) {
+    HRT_API_TRY
+    hrt_status st = check_adaptive(sc, cam, pr, R, rank, G, ad, pass, active_out);
+    if (st != HRT_OK) return st;
+    if (!sums || !sq || !count) return fail(HRT_ERR_INVALID, "NULL argument");
+    HIPCHK(hipSetDevice(sc->device));
+    hrt_stats prev;
+    st = hrt_scene_stats(sc, &prev);
+    if (st != HRT_OK) return st;
+    const size_t n = (size_t)hrt_stripe_rows(pr->height, R, rank, G) * pr->width;
+    *active_out = 0;
+    if (n) {
+        const size_t b_sums = n * 3 * sizeof(float), b_sq = n * sizeof(float), b_cnt = n * sizeof(int32_t);
+        char* d = nullptr;
+        hipError_t e = hipMalloc((void**)&d, b_sums + b_sq + b_cnt);
+        if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? HRT_ERR_OOM : HRT_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
+        float* d_sums = (float*)d; float* d_sq = (float*)(d + b_sums); int32_t* d_cnt = (int32_t*)(d + b_sums + b_sq);
+        hipError_t e1 = hipSuccess;
+        if (pass > 0) {
+            e1 = hipMemcpy(d_sums, sums, b_sums, hipMemcpyHostToDevice);
+            if (e1 == hipSuccess) e1 = hipMemcpy(d_sq, sq, b_sq, hipMemcpyHostToDevice);
+            if (e1 == hipSuccess) e1 = hipMemcpy(d_cnt, count, b_cnt, hipMemcpyHostToDevice);
+        }
+        if (e1 != hipSuccess) st = fail_hip(e1, "hipMemcpy H2D adaptive buffers");
+        else st = hrt_render_stripes_adaptive_device(sc, cam, pr, R, rank, G, ad, d_sums, d_sq, d_cnt, pass, active_out, nullptr);
+        if (st == HRT_OK && (pass == 0 || *active_out > 0)) {
+            hipError_t e2 = hipMemcpy(sums, d_sums, b_sums, hipMemcpyDeviceToHost);
+            if (e2 == hipSuccess) e2 = hipMemcpy(sq, d_sq, b_sq, hipMemcpyDeviceToHost);
+            if (e2 == hipSuccess) e2 = hipMemcpy(count, d_cnt, b_cnt, hipMemcpyDeviceToHost);
+            if (e2 != hipSuccess) st = fail_hip(e2, "hipMemcpy D2H adaptive buffers");
+        }
+        (void)hipFree(d);
+        if (st != HRT_OK) return st;
+    }
+    hrt_stats now;
+    st = hrt_scene_stats(sc, &now);
+    if (st != HRT_OK) return st;
+    if (stats) *stats = now;
+    return HRT_OK;
+    HRT_API_CATCH
+}
+
+hrt_status hrt_adaptive_mean_device(hrt_scene* sc, const float* d_sums, const int32_t* d_count, int64_t n_pixels, float* d_mean, void* stream) {
+    HRT_API_TRY
+    if (!sc || !d_sums || !d_count || !d_mean || n_pixels < 0) return fail(HRT_ERR_INVALID, "bad argument");
+    if (n_pixels == 0) return HRT_OK;
+    HIPCHK(hipSetDevice(sc->device));
+    const int blocks = (int)std::min<int64_t>((n_pixels + 255) / 256, (int64_t)sc->n_cus * 8);
+    hipLaunchKernelGGL(k_ad_mean, dim3(blocks), dim3(256), 0, (hipStream_t)stream, d_sums, d_count, (long long)n_pixels, d_mean);
+    HIPCHK(hipGetLastError());
     return HRT_OK;
     HRT_API_CATCH
 }

@@ -14,13 +14,19 @@
 //     --lens (thin-lens sampling with the scene's `aperture`: camera.h:34's commented-out circularRand(lensRadius); off = the reference)
 //     --no-progress (no reporter thread and no progress counter on the device: main.cpp:97-109), --progress-ms N (its interval, 500)
 //     --rccl (gather the film through an RCCL communicator even on one GPU; with --gpus N > 1 it always is)
+//     --adaptive T (adaptive sampling: a pixel stops once the relative standard error of its mean luminance is below T;
+//         one GPU, no --checkpoint / --resume)   --min-samples N (what every pixel takes first, 16)   --progressive N (the
+//         samples a pass adds to the pixels still active, 16)   --adaptive-floor F (luminance floor of the relative error, 0.01)
+//     --sample-map FILE.pfm (with --adaptive: the samples each pixel took, as floats in all three channels)
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <iomanip>
+#include <cmath>
 #include <iostream>
 #include <string>
+#include <vector>
 
 #include "../../include/hrt_host.h"
 #include "assets.h"
@@ -43,10 +49,17 @@ static void printElapsed(const char* what, std::chrono::high_resolution_clock::t
 int main(int argc, char** argv) {
     auto start = std::chrono::high_resolution_clock::now();
     std::string file = "teapot_scene.yaml";  // main.cpp:146
-    std::string assets, out, makeAssets, dumpLinear;
+    std::string assets, out, makeAssets, dumpLinear, sampleMap;
     RenderOptions opt;
     int spp = -1, sw = -1, sh = -1;
     bool haveFile = false;
+    // a non-negative finite number, or exit 2 (before anything has touched a device)
+    auto number = [](const char* flag, const char* v) -> float {
+        char* end = nullptr;
+        const double x = std::strtod(v, &end);
+        if (end == v || *end != '\0' || !std::isfinite(x) || x < 0.0) { std::cerr << flag << " takes a number >= 0" << std::endl; std::exit(2); }
+        return (float)x;
+    };
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i];
         auto next = [&](const char* flag) -> const char* {
@@ -78,8 +91,18 @@ int main(int argc, char** argv) {
         else if (a == "--resume") opt.resume = true;
         else if (a == "--max-passes") opt.max_passes = std::atoi(next("--max-passes"));
         else if (a == "--dump-linear") dumpLinear = next("--dump-linear");
+        else if (a == "--adaptive") opt.adaptive = number("--adaptive", next("--adaptive"));
+        else if (a == "--adaptive-floor") opt.adaptive_floor = number("--adaptive-floor", next("--adaptive-floor"));
+        else if (a == "--min-samples") opt.min_samples = std::atoi(next("--min-samples"));
+        else if (a == "--sample-map") sampleMap = next("--sample-map");
         else if (!haveFile) { file = a; haveFile = true; }
     }
+    if (opt.adaptive >= 0.0f) {
+        const char* why = opt.gpus > 1 ? "--gpus N > 1" : !opt.checkpoint.empty() ? "--checkpoint" : opt.resume ? "--resume" : nullptr;
+        if (why) { std::cerr << "--adaptive cannot be combined with " << why << std::endl; return 2; }
+        if (opt.min_samples < 2) { std::cerr << "--min-samples must be >= 2" << std::endl; return 2; }
+        if (opt.pass_samples <= 0) opt.pass_samples = 16;
+    } else if (!sampleMap.empty()) { std::cerr << "--sample-map needs --adaptive" << std::endl; return 2; }
     if (!makeAssets.empty()) {
         long t = writeTeapotObj(makeAssets + "/teapot.obj", 1.0);
         long b = writeBustObj(makeAssets + "/marble_bust_01.obj", 1.0);
@@ -106,6 +129,9 @@ int main(int argc, char** argv) {
     const double load_s = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - start).count();
 
     if (opt.resume && opt.checkpoint.empty()) { std::cerr << "--resume needs --checkpoint FILE" << std::endl; return 2; }
+    if (opt.adaptive >= 0.0f && film->getFilm().samples < 2) { std::cerr << "--adaptive needs at least 2 samples per pixel" << std::endl; return 2; }
+    std::vector<int32_t> counts;
+    if (opt.adaptive >= 0.0f) opt.sample_counts = &counts;
     if (opt.pass_samples > 0) opt.on_pass = [&film](int) { film->outputFilm(); };   // preview image after every pass
     hrt_stats stats{};
     double seconds = 0.0;
@@ -117,18 +143,32 @@ int main(int argc, char** argv) {
         std::cerr << "cannot write " << dumpLinear << std::endl;
         return -1;
     }
+    if (!sampleMap.empty()) {
+        std::vector<float> m(counts.size() * 3);
+        for (size_t i = 0; i < counts.size(); ++i) m[3 * i] = m[3 * i + 1] = m[3 * i + 2] = (float)counts[i];
+        if (!writePFM(sampleMap, m.data(), film->getFilm().width, film->getFilm().height)) {
+            std::cerr << "cannot write " << sampleMap << std::endl;
+            return -1;
+        }
+    }
 
     if (opt.stats || std::getenv("HRT_STATS")) {
         const double bytes = 32.0 * stats.box_tests + 36.0 * stats.tri_tests + 60.0 * stats.mesh_hits + 12.0 * stats.env_lookups +
                              12.0 * film->getFilm().width * film->getFilm().height;
         // wall_s: the reference's own stopwatch (main.cpp:144,184): process start to after the image file is written
         const double wall_s = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - start).count();
+        char extra[160] = "";
+        if (opt.adaptive >= 0.0f) {   // the samples adaptive sampling took, and their share of the uniform render's
+            const double uniform = (double)film->getFilm().width * film->getFilm().height * film->getFilm().samples;
+            std::snprintf(extra, sizeof(extra), ", \"adaptive_threshold\": %g, \"samples_taken\": %llu, \"sample_fraction\": %.6f",
+                          opt.adaptive, (unsigned long long)stats.samples, (double)stats.samples / uniform);
+        }
         std::printf("{\"rays\": %llu, \"samples\": %llu, \"box_tests\": %llu, \"tri_tests\": %llu, \"render_s\": %.6f, "
                     "\"kernel_ms\": %.3f, \"mrays_per_s\": %.3f, \"msamples_per_s\": %.3f, \"algorithmic_gb_per_s\": %.3f, "
-                    "\"load_s\": %.6f, \"wall_s\": %.6f, \"gpus\": %d}\n",
+                    "\"load_s\": %.6f, \"wall_s\": %.6f, \"gpus\": %d%s}\n",
                     (unsigned long long)stats.rays, (unsigned long long)stats.samples, (unsigned long long)stats.box_tests,
                     (unsigned long long)stats.tri_tests, seconds, stats.kernel_ms, stats.rays / seconds / 1e6,
-                    stats.samples / seconds / 1e6, stats.kernel_ms > 0 ? bytes / (stats.kernel_ms * 1e-3) / 1e9 : 0.0, load_s, wall_s, opt.gpus);
+                    stats.samples / seconds / 1e6, stats.kernel_ms > 0 ? bytes / (stats.kernel_ms * 1e-3) / 1e9 : 0.0, load_s, wall_s, opt.gpus, extra);
     }
     printElapsed("Done!", start);
     return r;  // main.cpp:194 (1 = success)

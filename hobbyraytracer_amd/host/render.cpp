@@ -75,6 +75,62 @@ bool readCheckpoint(const std::string& path, Checkpoint& ck, std::vector<float>&
     if (!ok) why = path + " is not a checkpoint of this film";
     return ok;
 }
+// The adaptive render on the first device (hrt.h hrt_render_stripes_adaptive): passes until no pixel is active, the film is
+// sums / count.  Host buffers: one stripe partition (G = 1) is the film in row order.
+hrt_status renderAdaptive(const hrt_flat_scene& flat, const hrt_camera& cam, hrt_params pr, std::shared_ptr<Film>& film,
+                          const RenderOptions& opt, hrt_stats* stats, double* render_seconds) {
+    const film_desc f = film->getFilm();
+    const int numPixels = f.width * f.height;
+    hrt_adaptive ad{};
+    ad.min_samples = std::min(opt.min_samples, f.samples);
+    ad.pass_samples = opt.pass_samples > 0 ? opt.pass_samples : 16;
+    ad.threshold = opt.adaptive;
+    ad.floor = opt.adaptive_floor;
+    hrt_scene* sc = nullptr;
+    hrt_status st = hrt_scene_create(&flat, 0, &sc);
+    if (st != HRT_OK) { std::cerr << "hrt_scene_create: " << hrt_status_str(st) << ": " << hrt_last_error() << std::endl; return st; }
+    std::vector<float> sums((size_t)numPixels * 3), sq((size_t)numPixels);
+    std::vector<int32_t> count((size_t)numPixels, 0);
+    std::vector<float>& lin = film->linear();
+    auto mean = [&]() {
+        for (size_t i = 0; i < (size_t)numPixels; ++i) {
+            const float c = static_cast<float>(count[i]);
+            for (int k = 0; k < 3; ++k) lin[3 * i + k] = sums[3 * i + k] / c;
+        }
+    };
+    const auto t0 = std::chrono::high_resolution_clock::now();
+    hrt_stats total{};
+    for (int pass = 0;; ++pass) {
+        int64_t active = 0;
+        hrt_stats ps{};
+        st = hrt_render_stripes_adaptive(sc, &cam, &pr, opt.rows_per_block, 0, 1, &ad, sums.data(), sq.data(), count.data(), pass, &active, &ps);
+        if (st != HRT_OK) break;
+        total.rays += ps.rays; total.samples += ps.samples; total.box_tests += ps.box_tests; total.tri_tests += ps.tri_tests;
+        total.mesh_hits += ps.mesh_hits; total.env_lookups += ps.env_lookups; total.launches += ps.launches;
+        total.traversal_box_tests += ps.traversal_box_tests; total.traversal_tri_tests += ps.traversal_tri_tests;
+        total.kernel_ms += ps.kernel_ms;
+        if (active == 0) break;
+        if (opt.progress) std::cout << "\rPass " << pass << ": " << active << "/" << numPixels << " pixels active" << std::flush;
+        if (opt.on_pass) {   // preview: the mean of every pixel's samples so far
+            mean();
+            st = hrt_resolve_u8(sc, lin.data(), numPixels, film->getPixels());
+            if (st != HRT_OK) break;
+            opt.on_pass((int)(total.samples / (uint64_t)numPixels));
+        }
+    }
+    if (st == HRT_OK) {
+        mean();
+        st = hrt_resolve_u8(sc, lin.data(), numPixels, film->getPixels());
+    }
+    if (st != HRT_OK) std::cerr << "\nadaptive render failed: " << hrt_status_str(st) << ": " << hrt_last_error() << std::endl;
+    const auto t1 = std::chrono::high_resolution_clock::now();
+    if (render_seconds) *render_seconds = std::chrono::duration<double>(t1 - t0).count();
+    if (opt.progress) std::cout << "\rPixels rendered: " << numPixels << "/" << numPixels << std::flush << "\n";
+    hrt_scene_destroy(sc);
+    if (opt.sample_counts) *opt.sample_counts = count;
+    if (stats) *stats = total;
+    return st;
+}
 }  // namespace
 
 hrt_status render(int /*nThreads*/, const std::shared_ptr<Texture> background, const std::shared_ptr<Hittable> world,
@@ -106,6 +162,8 @@ hrt_status render(int /*nThreads*/, const std::shared_ptr<Texture> background, c
     pr.max_depth = opt.max_depth; pr.t_min = 0.001f; pr.quirks = opt.quirks;
     pr.seed_lo = (uint32_t)opt.seed; pr.seed_hi = (uint32_t)(opt.seed >> 32);
     pr.flags = (opt.stats ? HRT_FLAG_STATS : 0) | (opt.thin_lens ? HRT_FLAG_THIN_LENS : 0) | (opt.progress ? HRT_FLAG_PROGRESS : 0);
+
+    if (opt.adaptive >= 0.0f) return renderAdaptive(flat, cam, pr, film, opt, stats, render_seconds);
 
     // The multi-GPU session: scene on every device, stripes accumulated in device memory, RCCL gather (hrt.h hrt_multi_*).
     hrt_multi* multi = nullptr;

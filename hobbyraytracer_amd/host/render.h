@@ -5,6 +5,7 @@
 #include <functional>
 #include <memory>
 #include <string>
+#include <vector>
 
 #include "classes.h"
 
@@ -31,6 +32,13 @@ struct RenderOptions {
     std::string checkpoint;
     bool resume = false;
     std::function<void(int samples_done)> on_pass;
+    // Adaptive sampling (hrt.h hrt_render_stripes_adaptive): adaptive >= 0 is the stopping threshold (the relative standard
+    // error of a pixel's mean luminance); every pixel takes min_samples, then passes of pass_samples (16 when 0) go to the
+    // pixels still above it.  One GPU, no checkpoints.  The film gets sums / count; sample_counts (optional) the counts.
+    float adaptive = -1.0f;
+    int min_samples = 16;
+    float adaptive_floor = 0.01f;       // luminance floor of the relative error's denominator (dark pixels)
+    std::vector<int32_t>* sample_counts = nullptr;
 };
 
 // render() of main.cpp:81-140.  nThreads is accepted and unused, exactly as in

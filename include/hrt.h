@@ -326,6 +326,44 @@ hrt_status hrt_render_stripes_accumulate_device(hrt_scene* scene, const hrt_came
 hrt_status hrt_render_stripes_accumulate(hrt_scene* scene, const hrt_camera* cam, const hrt_params* params,
                                          int32_t rows_per_block, int32_t rank, int32_t n_ranks, float* accum,
                                          int32_t sample_first, int32_t sample_count, hrt_stats* stats);
+/* ---- adaptive sampling ---------------------------------------------------
+ * Per-pixel sample counts driven by the noise of each pixel's mean luminance, rendered in passes over the row blocks of
+ * hrt_render_stripes_device.  Buffers use that stripe layout: d_sums 3 floats (running radiance sums, added in sample
+ * order, never divided), d_sq 1 float (running sum of Y*Y with Y = 0.2126f*r + 0.7152f*g + 0.0722f*b of each sample, in
+ * sample order, fp32 without contraction) and d_count 1 int32 (samples taken) per pixel.  Every path is keyed by
+ * (pixel, sample, bounce) as in the uniform render, so a pixel with count n holds exactly the sums of samples [0, n) of
+ * hrt_render_stripes_accumulate_device.
+ * Schedule: pass 0 takes samples [0, min_samples) of every pixel; pass k >= 1 adds min(pass_samples, samples - n) to every
+ * pixel still active, where n = min(samples, min_samples + (k - 1) * pass_samples) is the count all of them share (a stopped
+ * pixel never restarts).
+ * Stopping rule, in fp32, with n = count, m = Y(sums) / n, var = max(0, (sq - n*m*m) / (n - 1)): a pixel stops when
+ * n >= min_samples && var / n < (threshold * max(m, floor))^2, or when n == samples.  The comparison is strict (threshold 0
+ * never stops a pixel early) and a NaN keeps the pixel active until `samples`. */
+typedef struct hrt_adaptive {
+    int32_t min_samples;   /* pass 0 takes these for every pixel; 2 <= min_samples <= samples */
+    int32_t pass_samples;  /* each later pass adds these to every pixel still active; >= 1 */
+    float threshold;       /* relative standard error of the mean luminance at which a pixel stops; 0 = never */
+    float floor;           /* luminance floor of the relative error's denominator (dark pixels); >= 0 */
+} hrt_adaptive;
+
+/* One pass.  pass == 0 starts (the buffers need not be initialised); passes of one render run in order on one stream.  The
+ * active pixels are selected and compacted on the device; the call reads back their number (one 4-byte copy, synchronising
+ * `stream`) and enqueues the pass's render on `stream`.  *active_out = pixels rendered in this pass (0: the render is
+ * finished; nothing was enqueued).  HRT_ERR_INVALID for NULLs, min_samples outside [2, samples], pass_samples < 1, a negative
+ * or NaN threshold or floor, pass < 0; HRT_ERR_UNSUPPORTED with HRT_FLAG_MEGAKERNEL.  Samples and segments are counted
+ * (hrt_scene_stats: samples = those actually taken); HRT_FLAG_PROGRESS counts per pass. */
+hrt_status hrt_render_stripes_adaptive_device(hrt_scene* scene, const hrt_camera* cam, const hrt_params* params, int32_t rows_per_block,
+                                              int32_t rank, int32_t n_ranks, const hrt_adaptive* adaptive, float* d_sums, float* d_sq,
+                                              int32_t* d_count, int32_t pass, int64_t* active_out, void* stream);
+/* Blocking host-buffer form: the three buffers are uploaded first when pass > 0 and downloaded after a pass that rendered;
+ * `stats` (optional) describes this call only. */
+hrt_status hrt_render_stripes_adaptive(hrt_scene* scene, const hrt_camera* cam, const hrt_params* params, int32_t rows_per_block,
+                                       int32_t rank, int32_t n_ranks, const hrt_adaptive* adaptive, float* sums, float* sq,
+                                       int32_t* count, int32_t pass, int64_t* active_out, hrt_stats* stats);
+/* mean = sums / (float)count per pixel (3 floats each), on `stream`: a pixel with count == samples gets exactly the bits of
+ * the uniform render (main.cpp:126). */
+hrt_status hrt_adaptive_mean_device(hrt_scene* scene, const float* d_sums, const int32_t* d_count, int64_t n_pixels, float* d_mean,
+                                    void* stream);
 /* Blocking host-buffer form of the above (used by the CLI's one-thread-per-GPU
  * scheduler): same row layout, output copied to the caller-owned HOST buffer. */
 hrt_status hrt_render_stripes(hrt_scene* scene, const hrt_camera* cam, const hrt_params* params, int32_t rows_per_block,
