@@ -32,7 +32,7 @@ TEX_SOLID, TEX_CHECKER, TEX_IMAGE, TEX_ENV = range(4)
 MAX_XFORMS = 4
 Q1_ROTQ_NORMALIZE, Q2_TRI_NO_TMIN, Q3_TRI_NO_FACE, Q4_SHEAR_FROM_ORIGIN = 1, 2, 4, 8
 QUIRKS_REFERENCE, QUIRKS_FIXED = 0xF, 0x0
-FLAG_STATS, FLAG_MEGAKERNEL, FLAG_TIMING, FLAG_THIN_LENS, FLAG_PROGRESS = 1, 2, 4, 8, 16
+FLAG_STATS, FLAG_MEGAKERNEL, FLAG_TIMING, FLAG_THIN_LENS, FLAG_PROGRESS, FLAG_NEE = 1, 2, 4, 8, 16, 32
 
 
 # ---------------------------------------------------------------- structs (hrt.h)
@@ -103,7 +103,7 @@ class Stats(C.Structure):
     _fields_ = [("rays", C.c_uint64), ("samples", C.c_uint64), ("box_tests", C.c_uint64), ("tri_tests", C.c_uint64),
                 ("mesh_hits", C.c_uint64), ("env_lookups", C.c_uint64), ("kernel_ms", C.c_double), ("launches", C.c_uint64),
                 ("traversal_ms", C.c_double), ("traversal_launches", C.c_uint64),
-                ("traversal_box_tests", C.c_uint64), ("traversal_tri_tests", C.c_uint64)]
+                ("traversal_box_tests", C.c_uint64), ("traversal_tri_tests", C.c_uint64), ("shadow_rays", C.c_uint64)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -237,7 +237,8 @@ def _ptr(a, t=_fp):
 
 # ---------------------------------------------------------------- host side
 def default_params(width, height, samples, quirks=QUIRKS_REFERENCE, seed=0, max_depth=50, stats=False, megakernel=False, timing=False,
-                   thin_lens=False, progress=False):
+                   thin_lens=False, progress=False, nee=False):
+    """nee: next-event estimation with MIS for the scene's rect and sphere lights (FLAG_NEE)."""
     p = Params()
     _host.hrt_default_params(C.byref(p), width, height, samples)
     p.quirks = quirks
@@ -245,7 +246,7 @@ def default_params(width, height, samples, quirks=QUIRKS_REFERENCE, seed=0, max_
     p.seed_hi = (seed >> 32) & 0xFFFFFFFF
     p.max_depth = max_depth
     p.flags = (FLAG_STATS if stats else 0) | (FLAG_MEGAKERNEL if megakernel else 0) | (FLAG_TIMING if timing else 0) | \
-              (FLAG_THIN_LENS if thin_lens else 0) | (FLAG_PROGRESS if progress else 0)
+              (FLAG_THIN_LENS if thin_lens else 0) | (FLAG_PROGRESS if progress else 0) | (FLAG_NEE if nee else 0)
     return p
 
 

@@ -1163,8 +1163,10 @@ __device__ inline float matscalar_value(const DScene& sc, const hrt_matscalar& m
 
 // ------------------------------------------------------------------ Material::emitted / scatter (material.h, material.cpp)
 // Returns false when the path ends (DiffuseLight, absorbed Metal).
+// `lambert` (HRT_FLAG_NEE only; NULL otherwise): set to whether the scatter was Lambertian (a Lambertian, or a PBR whose mix
+// chose diffuse) -- the vertices that sample a light.
 __device__ inline bool material_scatter(const DScene& sc, const DRec& rec, vec3 rin_d, const rng_ctx& ctx, vec3& emitted,
-                                        vec3& attenuation, vec3& so, vec3& sd) {
+                                        vec3& attenuation, vec3& so, vec3& sd, bool* lambert = nullptr) {
     int mat_i = rec.mat;
     HRT_BOUNDS(2, mat_i, sc.n_mats);
     const hrt_material& m = sc.lmats[mat_i];
@@ -1191,6 +1193,7 @@ __device__ inline bool material_scatter(const DScene& sc, const DRec& rec, vec3 
         if (near_zero(scatterDirection)) scatterDirection = rec.normal;
         sd = scatterDirection;
         attenuation = (kind == HRT_MAT_UVTEST) ? rec.normal : matvec3_value(sc, m.albedo, rec.u, rec.v, rec.p);
+        if (lambert) *lambert = kind == HRT_MAT_LAMBERTIAN;
         return true;
     }
     if (kind == HRT_MAT_METAL) {  // material.h:166-177
@@ -1218,6 +1221,160 @@ __device__ inline bool material_scatter(const DScene& sc, const DRec& rec, vec3 
     else direction = refract(unitDirection, rec.normal, refractionRatio);
     sd = direction + matscalar_value(sc, m.s1, rec.u, rec.v, rec.p) * sph;
     return true;
+}
+
+
+// ------------------------------------------------------------------ next-event estimation (HRT_FLAG_NEE)
+// A light of the table hrt_scene_create builds: 3 x float4
+//   L0 = prim (bits), kind (bits), P_sel, cdf (the running sum of P_sel up to and including this light; the last one is 1)
+//   L1 = p[0..3]           (rect: a0, a1, b0, b1; sphere: cx, cy, cz, r)
+//   L2 = p[4], area, 0, 0  (rect: k)
+#define HRT_NEE_REC 3
+#define HRT_NEE_PI 3.14159265358979323846264338327950288f
+
+// Density (solid angle) of normalize(sd) for material_scatter's sd = n + sphericalRand(1), n = rec.normal of ANY length
+// (quirk Q-3 leaves mesh normals unnormalised, Q-9 leaves a zero normal).  With r = |n|, c = w.n, D = c^2 + 1 - r^2 the
+// direction w is met at the lengths t = c +- sqrt(D) of sd (|t w - n| = 1), and p_b(w) = sum over the positive roots of
+// t^2 / (4 pi sqrt(D)): c / pi for r = 1, 1 / (4 pi) for r = 0.  t0 / t1 = the positive roots (0 = none).  The roots are
+// formed without cancellation: the larger one directly, the other as (r^2 - 1) / it (the product of the roots).
+__device__ inline float nee_bsdf_pdf(vec3 n, vec3 w, float& t0, float& t1) {
+    const float c = dot(w, n);
+    const float rr1 = dot(n, n) - 1.0f;
+    const float D = c * c - rr1;
+    t0 = 0.0f; t1 = 0.0f;
+    if (!(D > 0.0f) || !(D < 3.0e38f)) return 0.0f;
+    const float sD = sqrtf(D);
+    const float big = c >= 0.0f ? c + sD : c - sD;
+    const float other = rr1 / big;
+    if (big > 0.0f) t0 = big;
+    if (other > 0.0f) t1 = other;
+    return (t0 * t0 + t1 * t1) / (4.0f * HRT_NEE_PI * sD);
+}
+// The root the shadow ray's direction is scaled by, chosen with probability t_k^2 / (t0^2 + t1^2): then d = t_k w has the
+// distribution of sd itself given its direction, so the shadow ray is a ray the bounce could have cast (quirk Q-1 makes a
+// wrapped mesh's t depend on |d|).
+__device__ inline float nee_pick_root(float t0, float t1, uint32_t u) {
+    const float a = t0 * t0, b = t1 * t1;
+    return u01(u) * (a + b) < a ? t0 : t1;
+}
+// The power heuristic's two weights, for densities a, b >= 0, written so that no inf * 0 or 0 / 0 can appear:
+//   nee_mis_bsdf(pb, q)   = pb^2 / (pb^2 + q^2)   (a bounce from an eligible vertex that hits a table light)
+//   nee_mis_shadow(pb, q) = pb q / (pb^2 + q^2)   (the light sample's weight times pb / q: its estimate is atten Le pb / q)
+__device__ inline float nee_clampf(float x) { return x < 3.0e38f ? x : 3.0e38f; }
+__device__ inline float nee_mis_bsdf(float pb, float q) {
+    pb = nee_clampf(pb); q = nee_clampf(q);
+    if (!(pb > 0.0f)) return 0.0f;
+    if (!(q > 0.0f)) return 1.0f;
+    if (pb >= q) { const float r = q / pb; return 1.0f / (1.0f + r * r); }
+    const float r = pb / q, r2 = r * r;
+    return r2 / (1.0f + r2);
+}
+__device__ inline float nee_mis_shadow(float pb, float q) {
+    pb = nee_clampf(pb); q = nee_clampf(q);
+    if (!(pb > 0.0f) || !(q > 0.0f)) return 0.0f;
+    const float r = pb < q ? pb / q : q / pb;
+    return r / (1.0f + r * r);
+}
+__device__ inline int nee_light_kind(float4 L0) { return __float_as_int(L0.y); }
+// Branchless orthonormal basis around the unit vector a (Duff et al., JCGT 2017).
+__device__ inline void nee_basis(vec3 a, vec3& b1, vec3& b2) {
+    const float sg = a.z >= 0.0f ? 1.0f : -1.0f;
+    const float k = -1.0f / (sg + a.z);
+    const float m = a.x * a.y * k;
+    b1 = vec3(1.0f + sg * a.x * a.x * k, sg * m, -sg * a.x);
+    b2 = vec3(m, sg + a.y * a.y * k, -a.y);
+}
+// Samples a direction w from x towards light (L0, L1, L2) with two uniforms; pl = its solid-angle density, `reach` = a distance
+// beyond the light's own along w (the shadow ray's t_max).  false: no direction (x on the rect's plane, zero distance).
+//   rect:   a uniform point y of the rect, pl = dist^2 / (A |cos theta_l|) (emission is two-sided, Q-14);
+//   sphere, x outside: w uniform in the cone the sphere subtends, pl = 1 / (2 pi (1 - cos theta_max));
+//   sphere, x inside: a uniform point y of the surface, pl = dist^2 / (A |cos theta_l|).
+__device__ inline bool nee_sample(float4 L0, float4 L1, float4 L2, vec3 x, uint32_t uy, uint32_t uz, vec3& w, float& pl, float& reach) {
+    const int kind = nee_light_kind(L0);
+    const float area = L2.y;
+    if (kind == HRT_PRIM_SPHERE) {
+        const vec3 c(L1.x, L1.y, L1.z);
+        const float r = L1.w;
+        const vec3 oc = c - x;
+        const float dc2 = dot(oc, oc);
+        if (dc2 > r * r) {
+            const float dc = sqrtf(dc2);
+            const float s2 = (r * r) / dc2;                        // sin^2 theta_max
+            const float omc = s2 / (1.0f + sqrtf(1.0f - s2));      // 1 - cos theta_max, without cancellation
+            const float om = u01(uy) * omc;                        // 1 - cos theta, uniform in [0, omc)
+            const float sn = sqrtf(om * (2.0f - om)), cs = 1.0f - om;
+            float sp, cp;
+            gsincos(u01(uz) * 6.283185307179586476925286766559f, sp, cp);
+            const vec3 a = oc / dc;
+            vec3 b1, b2;
+            nee_basis(a, b1, b2);
+            w = normalize((sn * cp) * b1 + (sn * sp) * b2 + cs * a);
+            pl = 1.0f / (2.0f * HRT_NEE_PI * omc);
+            reach = dc;                                            // the near side lies within the centre's distance
+            return omc > 0.0f && pl < 3.0e38f;
+        }
+        const float z = 1.0f - 2.0f * u01(uy);
+        const float sz = sqrtf(gmax(0.0f, 1.0f - z * z));
+        float sp, cp;
+        gsincos(u01(uz) * 6.283185307179586476925286766559f, sp, cp);
+        const vec3 nrm(sz * cp, sz * sp, z);
+        const vec3 dl = (c + r * nrm) - x;
+        const float d2 = dot(dl, dl), dist = sqrtf(d2);
+        if (!(dist > 0.0f)) return false;
+        w = dl / dist;
+        const float cl = fabsf(dot(w, nrm));
+        pl = d2 / (area * cl);
+        reach = dist;
+        return cl > 0.0f && pl < 3.0e38f;
+    }
+    const int axis = rect_axis(kind);
+    const float a = L1.x + u01(uy) * (L1.y - L1.x);
+    const float b = L1.z + u01(uz) * (L1.w - L1.z);
+    const vec3 y = axis == 0 ? vec3(L2.x, a, b) : (axis == 1 ? vec3(a, L2.x, b) : vec3(a, b, L2.x));
+    const vec3 dl = y - x;
+    const float d2 = dot(dl, dl), dist = sqrtf(d2);
+    if (!(dist > 0.0f)) return false;
+    w = dl / dist;
+    const float cl = fabsf(w[axis]);
+    pl = d2 / (area * cl);
+    reach = dist;
+    return cl > 0.0f && pl < 3.0e38f;
+}
+// The same density from the direction alone: pl of the unit direction w from x, given y = the point where the ray meets the
+// light (a bounce's hit record).  0 when w does not reach the light from x in the way nee_sample could have produced it.
+__device__ inline float nee_pdf(float4 L0, float4 L1, float4 L2, vec3 x, vec3 w, vec3 y) {
+    const int kind = nee_light_kind(L0);
+    const float area = L2.y;
+    const vec3 dl = y - x;
+    const float d2 = dot(dl, dl);
+    if (kind == HRT_PRIM_SPHERE) {
+        const vec3 c(L1.x, L1.y, L1.z);
+        const float r = L1.w;
+        const vec3 oc = c - x;
+        const float dc2 = dot(oc, oc);
+        if (dc2 > r * r) {
+            const float s2 = (r * r) / dc2;
+            const float omc = s2 / (1.0f + sqrtf(1.0f - s2));
+            return 1.0f / (2.0f * HRT_NEE_PI * omc);
+        }
+        const float cl = fabsf(dot(w, y - c)) / r;
+        return cl > 0.0f ? d2 / (area * cl) : 0.0f;
+    }
+    const float cl = fabsf(w[rect_axis(kind)]);
+    return cl > 0.0f ? d2 / (area * cl) : 0.0f;
+}
+// Light choice: the first light whose cdf exceeds u (the last light's cdf is 1).  L = the table (HRT_NEE_REC float4 each).
+template <class P>
+__device__ inline int nee_choose(P L, int n_lights, uint32_t u) {
+    const float x = u01(u);
+    int i = 0;
+    while (i + 1 < n_lights && !(x < L[HRT_NEE_REC * i].w)) ++i;
+    return i;
+}
+// Le of a light's hit record, as material_scatter's DiffuseLight branch (material.h:96-104) computes it
+__device__ inline vec3 nee_emitted(const DScene& sc, const DRec& rec) {
+    const hrt_material& m = sc.lmats[rec.mat];
+    return matvec3_value(sc, m.albedo, rec.u, rec.v, rec.p) * matscalar_value(sc, m.s0, rec.u, rec.v, rec.p);
 }
 
 // main.cpp:47-58

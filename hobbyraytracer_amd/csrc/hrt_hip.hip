@@ -13,6 +13,7 @@
 //   k_closest_hit       world->hit() for test rays (parity tests).
 //   k_math_probe        the shared math kernels, for CPU==GPU bit tests.
 //   k_ad_select / k_ad_scan / k_wf_reduce_list / k_ad_mean   adaptive sampling.
+//   k_wf_shade<STATS, true> / k_wf_shadow   next-event estimation with MIS, HRT_FLAG_NEE.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>   // types and prototypes only: the library is loaded on demand (rccl_api below)
 #include <dlfcn.h>
@@ -68,6 +69,7 @@ inline uint64_t fastdiv_magic(uint32_t d) { return d <= 1 ? 0 : (uint64_t)(~0ull
 struct DeviceCounters {      // 64-bit accumulators in device memory
     unsigned long long rays, samples, box_tests, tri_tests, mesh_hits, env_lookups;
     unsigned long long trav_box_tests, trav_tri_tests;   // the share of box_tests / tri_tests counted inside k_wf_ext launches
+    unsigned long long shadow_rays;                      // HRT_FLAG_NEE: shadow rays cast by k_wf_shadow
 #if defined(HRT_EXT_PROFILE) || defined(HRT_SHADE_PROFILE) || defined(HRT_STEP_PROFILE)       // experiments (tests/tools/ext_profile_run.py): where the lanes of k_wf_ext are, phase by phase
     unsigned long long prof[12];
 #endif
@@ -293,6 +295,14 @@ struct WfBuf {
     unsigned pull_k;             // tasks per pull
     unsigned group_q, group_r;   // n_tasks / n_groups, n_tasks % n_groups
     unsigned T, n_tasks;
+    // HRT_FLAG_NEE only (NULL / 0 otherwise):
+    float4* N[2];                // per position, double-buffered like S0..S3: shading normal.xyz, p_b of the direction the vertex
+                                 // scattered into (-1: the vertex does not sample lights); read back as "the previous vertex's p_b"
+    float4* direct;              // per SLOT: the running sum of the path's shadow terms, in vertex order (one writer per slot per round)
+    unsigned long long* wave_shadow;   // shadow rays per k_wf_shadow wave, folded into DeviceCounters::shadow_rays by the reduce
+    const float4* lights;        // the light table (hrt_device.h HRT_NEE_REC float4 per light)
+    const int32_t* light_of;     // per prim: its index in the table, -1 if it is not a table light
+    int n_lights;
 };
 // Task ownership.  Tasks differ in cost by orders of magnitude (a run of pixels under the mesh vs. a run of sky), so a
 // static wave -> task map leaves most waves idle while a few finish: plain striding (task = wave + i * n_waves) even
@@ -998,7 +1008,41 @@ __device__ inline void missq_flush(const DScene& sc, const WfBuf& w, MissQueue& 
 // The rest of the segment (analytic prims behind the last mesh, main.cpp:46-76) for every live path of one task, and,
 // for the survivors, the preparation of their next segment.  Survivors are written compacted, in order, to the other
 // state copy.  n = live paths of the task; returns the survivors (live_out) and the rays queued for the first mesh (qn_out).
+// HRT_FLAG_NEE: path_shade plus the multiple-importance weight of an emission that a bounce from an eligible vertex finds on a
+// table light (prev_pb = that vertex's p_b of the direction, -1: not eligible), and the record k_wf_shadow and the next round
+// read (nrec: shading normal, p_b of the new direction or -1).  The light sample itself is k_wf_shadow's.
 template <bool STATS>
+__device__ HRT_WAVE_FN bool path_shade_nee(const DScene& sc, const hrt_params& pr, const WfBuf& w, const rng_ctx& ctx, PathState& ps,
+                                           const WorldHit& wh, PathCounters& pc, float prev_pb, float4& nrec) {
+    if (STATS && sc.lprims[wh.prim].kind == HRT_PRIM_MESH) pc.mesh_hits++;
+    DRec rec;
+    hit_record(sc, wh, ps.o, ps.d, pr.quirks, pr.t_min, rec);
+    vec3 emitted, attenuation, so, sd;
+    bool lambert = false;
+    const bool b = material_scatter(sc, rec, ps.d, ctx, emitted, attenuation, so, sd, &lambert);
+    if (!b && prev_pb >= 0.0f) {
+        const int li = w.light_of[wh.prim];
+        if (li >= 0) {   // q from the ray's origin to the hit: the density the light strategy gives this direction
+            const float4 L0 = w.lights[HRT_NEE_REC * li], L1 = w.lights[HRT_NEE_REC * li + 1], L2 = w.lights[HRT_NEE_REC * li + 2];
+            const float q = L0.z * nee_pdf(L0, L1, L2, ps.o, normalize(ps.d), rec.p);
+            emitted = emitted * nee_mis_bsdf(prev_pb, q);
+        }
+    }
+    ps.result += ps.atten * emitted;
+    if (!b) return true;
+    ps.atten *= attenuation;
+    ps.o = so; ps.d = sd;
+    ps.bounce++;
+    nrec = make_float4(rec.normal.x, rec.normal.y, rec.normal.z, -1.0f);
+    if (lambert) {
+        float t0, t1;
+        const float pb = nee_bsdf_pdf(rec.normal, normalize(sd), t0, t1);
+        if (pb > 0.0f) nrec.w = pb;
+    }
+    return ps.bounce >= pr.max_depth;
+}
+
+template <bool STATS, bool NEE = false>
 __device__ HRT_WAVE_FN void wf_shade_task(const DScene& sc, const hrt_params& pr, const RenderMap& map, const WfScene& ws, unsigned n_local, int s0, int round,
                                      const WfBuf& w, unsigned task, unsigned n, unsigned lane, unsigned long long lt, MissQueue& mq,
                                      PathCounters& pc, unsigned& n_seg, unsigned& n_culled, unsigned& live_out, unsigned& qn_out, unsigned& rn_out) {
@@ -1044,8 +1088,11 @@ __device__ HRT_WAVE_FN void wf_shade_task(const DScene& sc, const hrt_params& pr
             }
         }
         HRT_SP_MARK(1);
+        float4 nrec = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
         if (j0 + lane < n && !missed) {
-            const bool ended = path_shade<STATS>(sc, pr, ctx, ps, wh, pc);
+            bool ended;
+            if (NEE) ended = path_shade_nee<STATS>(sc, pr, w, ctx, ps, wh, pc, round > 0 ? w.N[par][pos].w : -1.0f, nrec);
+            else ended = path_shade<STATS>(sc, pr, ctx, ps, wh, pc);
             if (ended) w.rad[slot] = make_float4(ps.result.x, ps.result.y, ps.result.z, 0.0f);
             else {
                 alive = true;
@@ -1069,6 +1116,7 @@ __device__ HRT_WAVE_FN void wf_shade_task(const DScene& sc, const hrt_params& pr
             ctx.bounce = (uint32_t)(round + 1);   // the next segment's draws (ConstantMedium::hit inside wf_prepare)
             enq = wf_prepare<STATS>(sc, pr, 0, ws.first_mesh, ws.has_mesh ? ws.first_mesh : -1, ps.o, ps.d, ctx, closest, prim, sub, mr, n_culled);
             wf_store_state(w, nxt, npos, ps, closest, slot, prim, sub);
+            if (NEE) w.N[nxt][npos] = nrec;
         }
         HRT_SP_MARK(3);
         out += (unsigned)__popcll(ma);
@@ -1096,7 +1144,7 @@ __device__ HRT_WAVE_FN void wf_shade_counters(const WfBuf& w, DeviceCounters* co
 #ifndef HRT_SHADE_WAVES
 #define HRT_SHADE_WAVES 4   // waves per SIMD the register allocator must leave room for (<= 128 VGPRs)
 #endif
-template <bool STATS>
+template <bool STATS, bool NEE>
 __global__ __launch_bounds__(256, HRT_SHADE_WAVES) void k_wf_shade(DScene sc, hrt_params pr, RenderMap map, WfScene ws, unsigned n_local, int s0, int round,
                                                   WfBuf w, DeviceCounters* counters) {
     const unsigned lane = threadIdx.x & 63u;
@@ -1114,11 +1162,96 @@ __global__ __launch_bounds__(256, HRT_SHADE_WAVES) void k_wf_shade(DScene sc, hr
     PathCounters pc; pc.rays = 0; pc.samples = 0; pc.mesh_hits = 0; pc.env_lookups = 0; pc.bvh.box_tests = 0; pc.bvh.tri_tests = 0;
     HRT_FOR_MY_TASKS(task, w, wave, lane) {
         unsigned live, qn, rn;
-        wf_shade_task<STATS>(sc, pr, map, ws, n_local, s0, round, w, task, HRT_UNIFORM(w.live[task]), lane, lt, mq, pc, n_seg, n_culled, live, qn, rn);
+        wf_shade_task<STATS, NEE>(sc, pr, map, ws, n_local, s0, round, w, task, HRT_UNIFORM(w.live[task]), lane, lt, mq, pc, n_seg, n_culled, live, qn, rn);
         if (lane == 0) { w.live[task] = live; w.qn[task] = qn; w.rn[task] = rn; if (rn) wf_ref_publish(w, task, rn); }
     }
     if (mq.count) missq_flush<STATS>(sc, w, mq, lane, mq.count, pc);
     wf_shade_counters<STATS>(w, counters, wave, lane, n_seg, n_culled, pc);
+}
+
+// HRT_FLAG_NEE, after round `round`'s k_wf_shade: for every survivor whose vertex is eligible (a Lambertian scatter: N.w >= 0), one
+// light sample.  Light and point from one RNG_LIGHT draw keyed by (pixel, sample, round); the shadow ray is the ray the bounce would
+// have cast in that direction (d = t_k w, a root of sd's length chosen by its share), traced by world_hit with t_max just beyond the
+// light; it sees the light exactly when the closest hit IS the sampled light's prim.  Its ConstantMedium draws use the bounce field
+// round | HRT_RNG_SHADOW.  The term atten Le pb q / (pb^2 + q^2) is added to the slot's `direct` sum.
+// The eligible positions are compacted per wave first (ballots into an LDS queue, as the miss queue of k_wf_shade does), so that the
+// world_hit of 64 shadow rays runs with full lanes whatever fraction of the survivors is eligible (metal, glass and media are not).
+// -DHRT_NEE_UNIT_SHADOW (experiment only): cast the shadow ray with the unit direction w instead of t_k w -- the biased
+// estimator the design avoids, kept compilable so the unbiasedness test can be shown to catch it.
+#define HRT_SHADOWQ_CAP 128
+__global__ __launch_bounds__(HRT_BLOCK) void k_wf_shadow(DScene sc, hrt_params pr, RenderMap map, unsigned n_local, int s0, int round, WfBuf w) {
+    __shared__ int s_stack[HRT_STACK_DEPTH * HRT_BLOCK];
+    __shared__ __attribute__((aligned(16))) uint32_t s_tables[HRT_TABLE_LDS_BYTES / 4];
+    __shared__ unsigned s_queue[HRT_BLOCK / 64][HRT_SHADOWQ_CAP];
+    int* stack = s_stack + threadIdx.x;
+    stage_tables(sc, s_tables);
+    const unsigned lane = threadIdx.x & 63u;
+    const unsigned wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    unsigned* const q = s_queue[threadIdx.x >> 6];
+    const int nxt = (round + 1) & 1;
+    unsigned n_shadow = 0;
+    unsigned qn = 0;                          // wave-uniform queue length
+    TaskPuller puller = HRT_TASK_PULLER(wave, w.n_groups);
+    unsigned task = 0, j0 = 0, n = 0;
+    bool have = wf_next_task(w, puller, lane, task);
+    if (have) n = HRT_UNIFORM(w.live[task]);
+    for (;;) {
+        // fill: whole 64-position chunks of this wave's tasks until 64 eligible positions wait (or the tasks are done)
+        while (have && qn < 64) {
+            if (j0 >= n) {
+                have = wf_next_task(w, puller, lane, task);
+                j0 = 0;
+                n = have ? HRT_UNIFORM(w.live[task]) : 0u;
+                continue;
+            }
+            const unsigned pos = task * w.T + j0 + lane;
+            const bool elig = j0 + lane < n && w.N[nxt][pos].w >= 0.0f;
+            const unsigned long long m = __ballot(elig);
+            if (elig) q[qn + lanes_below(m)] = pos;
+            qn += (unsigned)__popcll(m);          // < 64 + 64 <= HRT_SHADOWQ_CAP
+            j0 += 64;
+        }
+        const unsigned k = qn < 64 ? qn : 64u;
+        if (k == 0) break;
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        const unsigned pos = lane < k ? q[qn - k + lane] : 0u;
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        qn -= k;
+        if (lane >= k) continue;
+        const float4 nr = w.N[nxt][pos];
+        const float4 a = w.S0[nxt][pos], b = w.S1[nxt][pos];
+        const float az = w.S3[nxt][pos];
+        const unsigned slot = __float_as_uint(w.S2[nxt][pos].w);
+        rng_ctx ctx = slot_ctx(pr, map, slot, n_local, s0, round);
+        const u32x4 u = rng_draw(ctx, RNG_LIGHT, 0);
+        const int li = nee_choose(w.lights, w.n_lights, u.x);
+        const float4 L0 = w.lights[HRT_NEE_REC * li], L1 = w.lights[HRT_NEE_REC * li + 1], L2 = w.lights[HRT_NEE_REC * li + 2];
+        const vec3 x(a.x, a.y, a.z);
+        vec3 wd;
+        float pl, reach;
+        if (!nee_sample(L0, L1, L2, x, u.y, u.z, wd, pl, reach)) continue;
+        float t0, t1;
+        const float pb = nee_bsdf_pdf(vec3(nr.x, nr.y, nr.z), wd, t0, t1);
+        if (!(pb > 0.0f)) continue;
+#ifdef HRT_NEE_UNIT_SHADOW
+        const float tk = 1.0f;
+#else
+        const float tk = nee_pick_root(t0, t1, u.w);
+#endif
+        const vec3 d = tk * wd;
+        ctx.bounce = (uint32_t)round | HRT_RNG_SHADOW;
+        ++n_shadow;
+        DCounters cnt; cnt.box_tests = 0; cnt.tri_tests = 0;
+        const WorldHit wh = world_hit<false>(sc, x, d, pr.t_min, reach / tk * 1.001f, pr.quirks, ctx, stack, cnt);
+        if (wh.prim != __float_as_int(L0.x)) continue;
+        DRec rec;
+        hit_record(sc, wh, x, d, pr.quirks, pr.t_min, rec);
+        const vec3 term = vec3(b.z, b.w, az) * nee_emitted(sc, rec) * nee_mis_shadow(pb, L0.z * pl);
+        const float4 acc = w.direct[slot];
+        w.direct[slot] = make_float4(acc.x + term.x, acc.y + term.y, acc.z + term.z, 0.0f);
+    }
+    const unsigned c = wave_sum(n_shadow);
+    if (lane == 0 && c) w.wave_shadow[wave] += (unsigned long long)c;      // this wave's own cell
 }
 
 // Every remaining round [round0, rounds_end) of a task in one go, by the wave that pulled the task.  Rounds are a
@@ -1194,15 +1327,34 @@ __global__ __launch_bounds__(256, DEPTH <= 24 ? 4 : 3) void k_wf_tail(DScene sc,
 }
 
 // Per pixel: add the batch's samples IN SAMPLE ORDER (main.cpp:118-124); divide once all samples are in (main.cpp:126).
+// NEE: a sample's value is rad + direct (result + the shadow terms), formed before it is added.
+__device__ inline float4 wf_sample_value(const float4* __restrict__ rad, const float4* __restrict__ direct, size_t i, bool nee) {
+    float4 r = rad[i];
+    if (nee) { const float4 d = direct[i]; r.x = r.x + d.x; r.y = r.y + d.y; r.z = r.z + d.z; }
+    return r;
+}
+// (NEE: also the per-wave shadow-ray counts of the batch's k_wf_shadow launches)
+__device__ inline void wf_fold_shadow(DeviceCounters* counters, unsigned long long* __restrict__ wave_shadow, unsigned n_wave_rays) {
+    __shared__ unsigned long long total_s;
+    if (threadIdx.x == 0) total_s = 0;
+    __syncthreads();
+    unsigned long long mine = 0;
+    for (unsigned i = threadIdx.x; i < n_wave_rays; i += blockDim.x) { mine += wave_shadow[i]; wave_shadow[i] = 0; }
+    if (mine) atomicAdd(&total_s, mine);
+    __syncthreads();
+    if (threadIdx.x == 0 && total_s) atomicAdd(&counters->shadow_rays, total_s);
+}
+template <bool NEE>
 __global__ __launch_bounds__(256) void k_wf_reduce(const float4* __restrict__ rad, unsigned n_local, int chunk, int first_chunk, int last_chunk,
                                                    int spp, float* __restrict__ out, DeviceCounters* counters,
-                                                   unsigned long long* __restrict__ wave_rays, unsigned n_wave_rays) {
+                                                   unsigned long long* __restrict__ wave_rays, unsigned n_wave_rays,
+                                                   const float4* __restrict__ direct, unsigned long long* __restrict__ wave_shadow) {
     const unsigned stride = gridDim.x * blockDim.x;
     for (unsigned lp = blockIdx.x * blockDim.x + threadIdx.x; lp < n_local; lp += stride) {
         vec3 sum(0.0f);
         if (!first_chunk) sum = vec3(out[3ull * lp], out[3ull * lp + 1], out[3ull * lp + 2]);
         for (int s = 0; s < chunk; ++s) {
-            const float4 r = rad[(size_t)s * n_local + lp];
+            const float4 r = wf_sample_value(rad, direct, (size_t)s * n_local + lp, NEE);
             sum += vec3(r.x, r.y, r.z);
         }
         if (last_chunk) sum = sum / static_cast<float>(spp);
@@ -1220,6 +1372,7 @@ __global__ __launch_bounds__(256) void k_wf_reduce(const float4* __restrict__ ra
             if (total) atomicAdd(&counters->rays, total);
             atomicAdd(&counters->samples, (unsigned long long)n_local * (unsigned long long)chunk);
         }
+        if (NEE) wf_fold_shadow(counters, wave_shadow, n_wave_rays);
     }
 }
 
@@ -1269,10 +1422,12 @@ __device__ inline float ad_luma(float r, float g, float b) { return 0.2126f * r 
 
 // k_wf_reduce for a list batch: per list entry, the batch's samples IN SAMPLE ORDER into the pixel's sums and, as Y*Y, into
 // its sq; count = the samples summed so far.  Never divides (hrt_adaptive_mean_device does).
+template <bool NEE>
 __global__ __launch_bounds__(256) void k_wf_reduce_list(const float4* __restrict__ rad, const int32_t* __restrict__ pix, unsigned n_list,
                                                         int chunk, int first_chunk, int n_after, float* __restrict__ sums,
                                                         float* __restrict__ sq, int32_t* __restrict__ count, DeviceCounters* counters,
-                                                        unsigned long long* __restrict__ wave_rays, unsigned n_wave_rays) {
+                                                        unsigned long long* __restrict__ wave_rays, unsigned n_wave_rays,
+                                                        const float4* __restrict__ direct, unsigned long long* __restrict__ wave_shadow) {
     const unsigned stride = gridDim.x * blockDim.x;
     for (unsigned lp = blockIdx.x * blockDim.x + threadIdx.x; lp < n_list; lp += stride) {
         const size_t q = (size_t)(unsigned)pix[lp];
@@ -1280,7 +1435,7 @@ __global__ __launch_bounds__(256) void k_wf_reduce_list(const float4* __restrict
         float y2 = 0.0f;
         if (!first_chunk) { sum = vec3(sums[3 * q], sums[3 * q + 1], sums[3 * q + 2]); y2 = sq[q]; }
         for (int s = 0; s < chunk; ++s) {
-            const float4 r = rad[(size_t)s * n_list + lp];
+            const float4 r = wf_sample_value(rad, direct, (size_t)s * n_list + lp, NEE);
             sum += vec3(r.x, r.y, r.z);
             const float y = ad_luma(r.x, r.y, r.z);
             y2 += y * y;
@@ -1301,6 +1456,7 @@ __global__ __launch_bounds__(256) void k_wf_reduce_list(const float4* __restrict
             if (total) atomicAdd(&counters->rays, total);
             atomicAdd(&counters->samples, (unsigned long long)n_list * (unsigned long long)chunk);
         }
+        if (NEE) wf_fold_shadow(counters, wave_shadow, n_wave_rays);
     }
 }
 
@@ -1418,6 +1574,7 @@ struct WfWorkspace {          // device workspace of the wavefront pipeline (gro
     size_t bytes = 0;
     size_t slots = 0;
     int depth = 0, n_mesh = 0;
+    bool nee = false;            // holds the HRT_FLAG_NEE buffers (WfBuf::N, direct, wave_shadow)
     WfBuf buf{};
 };
 
@@ -1448,6 +1605,10 @@ struct hrt_scene {
     int32_t* d_ad_pix = nullptr;
     unsigned* d_ad_blocks = nullptr;
     size_t ad_cap = 0;
+    // HRT_FLAG_NEE: the light table (hrt_device.h HRT_NEE_REC float4 per light) and the prim -> light map, built at hrt_scene_create
+    float4* d_lights = nullptr;
+    int32_t* d_light_of = nullptr;
+    int n_lights = 0;
 };
 
 namespace {
@@ -1576,6 +1737,57 @@ hrt_status validate(const hrt_flat_scene* f) {
     return HRT_OK;
 }
 
+
+// HRT_FLAG_NEE's light table: the unwrapped XY / XZ / YZ rects and spheres (radius > 0) whose material is DiffuseLight and whose
+// parameters are finite, with a selection probability proportional to a power proxy: area x luminance of the constant emission
+// colour x the constant strength (1 for a factor that comes from a texture).  Lights whose proxy is 0, negative or not finite are
+// left out (they, and every other emitter, still emit with weight 1 when a bounce hits them).  Returns the number of lights;
+// `lights` gets HRT_NEE_REC float4 per light (hrt_device.h), light_of one entry per prim (-1: not a table light).
+int build_light_table(const hrt_flat_scene* f, std::vector<float>& lights, std::vector<int32_t>& light_of) {
+    light_of.assign(f->n_prims, -1);
+    std::vector<std::pair<uint32_t, double>> cand;
+    double total = 0.0;
+    for (uint32_t i = 0; i < f->n_prims; ++i) {
+        const hrt_prim& p = f->prims[i];
+        if (p.n_xforms != 0 || f->materials[p.material].kind != HRT_MAT_DIFFUSE_LIGHT) continue;
+        double area;
+        if (p.kind == HRT_PRIM_SPHERE) {
+            if (!std::isfinite(p.p[0]) || !std::isfinite(p.p[1]) || !std::isfinite(p.p[2]) || !std::isfinite(p.p[3]) || !(p.p[3] > 0.0f)) continue;
+            area = 4.0 * 3.14159265358979323846 * (double)p.p[3] * (double)p.p[3];
+        } else if (p.kind == HRT_PRIM_XY_RECT || p.kind == HRT_PRIM_XZ_RECT || p.kind == HRT_PRIM_YZ_RECT) {
+            bool ok = true;
+            for (int k = 0; k < 5; ++k) ok = ok && std::isfinite(p.p[k]);
+            if (!ok || !(p.p[1] > p.p[0]) || !(p.p[3] > p.p[2])) continue;
+            area = ((double)p.p[1] - p.p[0]) * ((double)p.p[3] - p.p[2]);
+        } else continue;
+        const hrt_material& m = f->materials[p.material];
+        const double lum = m.albedo.tex < 0 ? 0.2126 * m.albedo.c[0] + 0.7152 * m.albedo.c[1] + 0.0722 * m.albedo.c[2] : 1.0;
+        const double strength = m.s0.tex < 0 ? (double)m.s0.c : 1.0;
+        const double proxy = area * lum * strength;
+        if (!(proxy > 0.0) || !std::isfinite(proxy) || !std::isfinite((float)area)) continue;
+        cand.push_back({i, proxy});
+        total += proxy;
+    }
+    if (cand.empty() || !std::isfinite(total)) return 0;
+    lights.clear();
+    double run = 0.0;
+    for (size_t k = 0; k < cand.size(); ++k) {
+        const hrt_prim& p = f->prims[cand[k].first];
+        run += cand[k].second;
+        const float psel = (float)(cand[k].second / total);
+        const float cdf = k + 1 == cand.size() ? 1.0f : (float)(run / total);
+        const double area = p.kind == HRT_PRIM_SPHERE ? 4.0 * 3.14159265358979323846 * (double)p.p[3] * (double)p.p[3]
+                                                      : ((double)p.p[1] - p.p[0]) * ((double)p.p[3] - p.p[2]);
+        int32_t prim_bits = (int32_t)cand[k].first, kind_bits = p.kind;
+        float fp, fk;
+        memcpy(&fp, &prim_bits, 4); memcpy(&fk, &kind_bits, 4);
+        const float rec[4 * HRT_NEE_REC] = {fp, fk, psel, cdf, p.p[0], p.p[1], p.p[2], p.p[3], p.kind == HRT_PRIM_SPHERE ? 0.0f : p.p[4], (float)area, 0.0f, 0.0f};
+        lights.insert(lights.end(), rec, rec + 4 * HRT_NEE_REC);
+        light_of[cand[k].first] = (int32_t)k;
+    }
+    return (int)cand.size();
+}
+
 // Depth of a (validated) mesh BVH: the deepest inner node, root = 1 (what validate() bounds by HRT_STACK_DEPTH).
 int bvh_depth(const hrt_flat_scene* f, const hrt_mesh& m) {
     int deepest = 0;
@@ -1603,6 +1815,7 @@ hrt_status check_params(const hrt_params* p) {
     // the wavefront pipeline enqueues two launches and 3 KB of counters per round whether paths are left or not
     if (p->max_depth > 65536) return fail(HRT_ERR_UNSUPPORTED, "max_depth above 65536 (the reference's is 50, main.cpp:32)");
     if (!(p->t_min == p->t_min)) return fail(HRT_ERR_INVALID, "t_min is NaN");
+    if ((p->flags & HRT_FLAG_MEGAKERNEL) && (p->flags & HRT_FLAG_NEE)) return fail(HRT_ERR_UNSUPPORTED, "next-event estimation renders on the wavefront pipeline only");
     return HRT_OK;
 }
 
@@ -1630,13 +1843,14 @@ hrt_status launch_megakernel(hrt_scene* sc, const hrt_camera* cam, const hrt_par
 // whose paths die early (open scenes: C4 shiny_teapot spends 22 batches at a 48 Mi cap, 141 ms; 2 batches, 91 ms) want
 // the largest batch that fits: 184 B per slot, up to 60 % of the free HBM (288 GB per MI355X) and 2^31 slots.  The
 // workspace is only ever as large as the batch needs (the headline frame: 41 M slots = 7.5 GB).
-size_t wf_max_slots(const hrt_scene* sc) {
+// (HRT_FLAG_NEE: 48 B more per slot, WfBuf::N and direct)
+size_t wf_max_slots(const hrt_scene* sc, bool nee = false) {
     if (const char* e = getenv("HRT_WF_MAX_SLOTS")) { long long v = atoll(e); if (v > 0) return (size_t)v; }
     size_t cap = (size_t)48 << 20;
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
         free_b += sc->wf.bytes;                          // what we hold already can be re-used
-        cap = std::max(cap, (size_t)((double)free_b * 0.6 / 184.0));
+        cap = std::max(cap, (size_t)((double)free_b * 0.6 / (nee ? 232.0 : 184.0)));
     }
     return std::min(cap, (size_t)1 << 31);
 }
@@ -1647,10 +1861,10 @@ size_t wf_counter_words(int depth, int n_mesh) { return (size_t)256 * (2 + (size
 // ... and of 512 words per traversal launch for its ref-walk lists (WfBuf::ref_prod / ref_cons), + one block nobody reads
 size_t wf_ref_counter_words(int depth, int n_mesh) { return (size_t)512 * ((size_t)depth * (size_t)std::max(1, n_mesh) + 1); }
 
-hrt_status wf_reserve(hrt_scene* sc, size_t slots, int depth) {
+hrt_status wf_reserve(hrt_scene* sc, size_t slots, int depth, bool nee) {
     WfWorkspace& w = sc->wf;
     const int n_mesh = (int)sc->mesh_prims.size();
-    if (w.base && w.slots >= slots && w.depth >= depth && w.n_mesh == n_mesh) return HRT_OK;
+    if (w.base && w.slots >= slots && w.depth >= depth && w.n_mesh == n_mesh && (w.nee || !nee)) return HRT_OK;
     if (w.base) { HIPCHK(hipDeviceSynchronize()); (void)hipFree(w.base); w = WfWorkspace(); }
     const size_t max_tasks = slots / 64 + 1;   // the smallest task HRT_WF_TASK_SIZE can ask for is 64 positions (the default is >= 256)
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
@@ -1659,7 +1873,8 @@ hrt_status wf_reserve(hrt_scene* sc, size_t slots, int depth) {
     const size_t ctr_words = wf_counter_words(depth, n_mesh) + wf_ref_counter_words(depth, n_mesh);
     const size_t ref_cap = max_tasks / HRT_REF_GROUPS + 1;
     const size_t total = (sc->ds.stale_ff ? 12 : 11) * f4 + 2 * i4 + 3 * al(max_tasks * sizeof(unsigned)) + al(ctr_words * sizeof(unsigned)) + al(ref_cap * HRT_REF_GROUPS * sizeof(uint2)) +
-                         al((size_t)sc->n_cus * 32 * sizeof(unsigned long long));                                      // 184 B per slot
+                         al((size_t)sc->n_cus * 32 * sizeof(unsigned long long)) +                                     // 184 B per slot
+                         (nee ? 3 * f4 + al((size_t)sc->n_cus * 32 * sizeof(unsigned long long)) : 0);                 // + 48 with NEE
     void* base = nullptr;
     hipError_t e = hipMalloc(&base, total);
     if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? HRT_ERR_OOM : HRT_ERR_HIP, std::string("hipMalloc(wavefront workspace): ") + hipGetErrorString(e));
@@ -1680,7 +1895,12 @@ hrt_status wf_reserve(hrt_scene* sc, size_t slots, int depth) {
     w.buf.n_wave_rays = (unsigned)sc->n_cus * 8u * 4u;           // k_wf_shade never runs more waves (task_blocks <= 8 per CU, 4 waves each)
     w.buf.wave_rays = (unsigned long long*)take(al((size_t)w.buf.n_wave_rays * sizeof(unsigned long long)));
     HIPCHK(hipMemset(w.buf.wave_rays, 0, (size_t)w.buf.n_wave_rays * sizeof(unsigned long long)));
-    w.base = base; w.bytes = total; w.slots = slots; w.depth = depth; w.n_mesh = n_mesh;
+    if (nee) {
+        w.buf.N[0] = (float4*)take(f4); w.buf.N[1] = (float4*)take(f4); w.buf.direct = (float4*)take(f4);
+        w.buf.wave_shadow = (unsigned long long*)take(al((size_t)w.buf.n_wave_rays * sizeof(unsigned long long)));
+        HIPCHK(hipMemset(w.buf.wave_shadow, 0, (size_t)w.buf.n_wave_rays * sizeof(unsigned long long)));
+    }
+    w.base = base; w.bytes = total; w.slots = slots; w.depth = depth; w.n_mesh = n_mesh; w.nee = nee;
     return HRT_OK;
 }
 
@@ -1693,7 +1913,9 @@ hrt_status launch_wavefront(hrt_scene* sc, const hrt_camera* cam, const hrt_para
     const unsigned n_local = map_pixels(map);
     const int D = pr->max_depth;
     const int n_mesh = (int)sc->mesh_prims.size();
-    size_t cap = wf_max_slots(sc);
+    // HRT_FLAG_NEE in a scene without table lights is the default render: nothing would differ
+    const bool nee = (pr->flags & HRT_FLAG_NEE) != 0 && sc->n_lights > 0;
+    size_t cap = wf_max_slots(sc, nee);
     const int s_end = s_first + s_count;
     int chunk = (int)std::min<size_t>((size_t)s_count, std::max<size_t>(1, cap / n_local));
     // (the largest batches that fit plus a remainder, NOT equal batches: C4 on one GPU takes 92.8 ms as 453 + 59 samples and
@@ -1702,12 +1924,13 @@ hrt_status launch_wavefront(hrt_scene* sc, const hrt_camera* cam, const hrt_para
     for (;;) {   // the memory estimate can be stale (other processes on the device): halve the batch on OOM
         const size_t slots = (size_t)n_local * chunk;
         if (slots >= ((size_t)1 << 32) - 4096) return fail(HRT_ERR_UNSUPPORTED, "tile too large for 32-bit slot ids");
-        st = wf_reserve(sc, slots, D);
+        st = wf_reserve(sc, slots, D, nee);
         if (st != HRT_ERR_OOM || chunk == 1) break;
         chunk = (chunk + 1) / 2;
     }
     if (st != HRT_OK) return st;
     WfBuf w = sc->wf.buf;
+    if (nee) { w.lights = sc->d_lights; w.light_of = sc->d_light_of; w.n_lights = sc->n_lights; }
     WfScene ws;
     ws.has_mesh = n_mesh > 0;
     ws.first_mesh = n_mesh > 0 ? sc->mesh_prims.front() : sc->n_prims;
@@ -1728,6 +1951,7 @@ hrt_status launch_wavefront(hrt_scene* sc, const hrt_camera* cam, const hrt_para
     if (n_mesh > HRT_TAIL_MAX_MESHES) tail_round = D;
     const bool stale_ff = sc->ds.stale_ff && (pr->quirks & HRT_Q3_TRI_NO_FACE);
     if (stale_ff) tail_round = D;        // k_wf_tail has no stage for the stale frontFace (k_wf_stale): round by round
+    if (nee) tail_round = D;             // ... nor for the light samples (k_wf_shadow)
     tail_round = std::min(tail_round, D);
     int leaf_num = 48;                                   // k_wf_ext: start the leaf phase when >= 48/64 of the busy lanes wait at a leaf
     if (const char* e = getenv("HRT_EXT_LEAF_NUM")) leaf_num = atoi(e);
@@ -1793,6 +2017,7 @@ hrt_status launch_wavefront(hrt_scene* sc, const hrt_camera* cam, const hrt_para
             w.pull_k = (w.n_tasks <= waves && !force_dynamic) ? 0u : std::min(32u, std::max(1u, w.n_tasks / (waves * 4u)));
             w.group_q = w.n_tasks / w.n_groups; w.group_r = w.n_tasks % w.n_groups;
         };
+        if (nee) HIPCHK(hipMemsetAsync(w.direct, 0, (size_t)n_slots * sizeof(float4), stream));   // the shadow sums start at +0.0f
         next_counters((unsigned)task_blocks * 4u);
         w.ref_prod = ref_block(0, 0); w.ref_cons = ref_block(D, 0);
         if (stats) hipLaunchKernelGGL(k_wf_gen<true>, dim3(task_blocks), dim3(256), 0, stream, sc->ds, *cam, *pr, map, ws, n_local, s0, n_slots, w, sc->d_counters);
@@ -1828,8 +2053,16 @@ hrt_status launch_wavefront(hrt_scene* sc, const hrt_camera* cam, const hrt_para
             }
             next_counters((unsigned)task_blocks * 4u);
             w.ref_prod = ref_block(r + 1, 0); w.ref_cons = ref_block(D, 0);
-            if (stats) hipLaunchKernelGGL(k_wf_shade<true>, dim3(task_blocks), dim3(256), 0, stream, sc->ds, *pr, map, ws, n_local, s0, r, w, sc->d_counters);
-            else hipLaunchKernelGGL(k_wf_shade<false>, dim3(task_blocks), dim3(256), 0, stream, sc->ds, *pr, map, ws, n_local, s0, r, w, sc->d_counters);
+            if (nee) {
+                if (stats) hipLaunchKernelGGL((k_wf_shade<true, true>), dim3(task_blocks), dim3(256), 0, stream, sc->ds, *pr, map, ws, n_local, s0, r, w, sc->d_counters);
+                else hipLaunchKernelGGL((k_wf_shade<false, true>), dim3(task_blocks), dim3(256), 0, stream, sc->ds, *pr, map, ws, n_local, s0, r, w, sc->d_counters);
+                if (r + 1 < D) {   // survivors of the last round: none (bounce + 1 < max_depth)
+                    // (launches per round with NEE: pre + ext per mesh, stale, shade, shadow <= the 2 * max(1, n_mesh) + 2 of wf_counter_words)
+                    next_counters((unsigned)task_blocks * 4u);
+                    hipLaunchKernelGGL(k_wf_shadow, dim3(task_blocks), dim3(HRT_BLOCK), 0, stream, sc->ds, *pr, map, n_local, s0, r, w);
+                }
+            } else if (stats) hipLaunchKernelGGL((k_wf_shade<true, false>), dim3(task_blocks), dim3(256), 0, stream, sc->ds, *pr, map, ws, n_local, s0, r, w, sc->d_counters);
+            else hipLaunchKernelGGL((k_wf_shade<false, false>), dim3(task_blocks), dim3(256), 0, stream, sc->ds, *pr, map, ws, n_local, s0, r, w, sc->d_counters);
             if (progress)   // paths ended so far = earlier batches + this batch's slots - the live ones (w.live, as k_wf_shade left it)
                 hipLaunchKernelGGL(k_wf_progress, dim3(1), dim3(256), 0, stream, w.live, w.n_tasks, sc->progress_base + n_slots, sc->d_progress);
         }
@@ -1849,9 +2082,11 @@ hrt_status launch_wavefront(hrt_scene* sc, const hrt_camera* cam, const hrt_para
         }
         const int rblocks = (int)std::min<size_t>((n_local + 255) / 256, (size_t)sc->n_cus * 8);
         if (map.mode == 2)
-            hipLaunchKernelGGL(k_wf_reduce_list, dim3(rblocks), dim3(256), 0, stream, w.rad, map.pix, n_local, c, s0 == 0 ? 1 : 0, s0 + c, d_out, d_sq, d_count, sc->d_counters, w.wave_rays, w.n_wave_rays);
+            hipLaunchKernelGGL(nee ? k_wf_reduce_list<true> : k_wf_reduce_list<false>, dim3(rblocks), dim3(256), 0, stream, w.rad, map.pix, n_local, c, s0 == 0 ? 1 : 0, s0 + c, d_out, d_sq, d_count,
+                               sc->d_counters, w.wave_rays, w.n_wave_rays, (const float4*)w.direct, w.wave_shadow);
         else
-            hipLaunchKernelGGL(k_wf_reduce, dim3(rblocks), dim3(256), 0, stream, w.rad, n_local, c, s0 == 0 ? 1 : 0, s0 + c >= pr->samples ? 1 : 0, pr->samples, d_out, sc->d_counters, w.wave_rays, w.n_wave_rays);
+            hipLaunchKernelGGL(nee ? k_wf_reduce<true> : k_wf_reduce<false>, dim3(rblocks), dim3(256), 0, stream, w.rad, n_local, c, s0 == 0 ? 1 : 0, s0 + c >= pr->samples ? 1 : 0, pr->samples, d_out,
+                               sc->d_counters, w.wave_rays, w.n_wave_rays, (const float4*)w.direct, w.wave_shadow);
         if (progress) {
             sc->progress_base += n_slots;
             hipLaunchKernelGGL(k_set_progress, dim3(1), dim3(1), 0, stream, sc->progress_base, sc->d_progress);
@@ -2078,6 +2313,18 @@ hrt_status hrt_scene_create(const hrt_flat_scene* f, int device, hrt_scene** out
     sc->ds.lprims = d_prims; sc->ds.lmats = d_mats; sc->ds.ltexs = d_texs; sc->ds.lmeshes = d_meshes;
     sc->ds.n_mats = (int32_t)f->n_materials; sc->ds.n_texs = (int32_t)f->n_textures; sc->ds.n_meshes = (int32_t)f->n_meshes;
     sc->n_prims = (int)f->n_prims;
+    {   // HRT_FLAG_NEE's light table
+        std::vector<float> lights;
+        std::vector<int32_t> light_of;
+        sc->n_lights = build_light_table(f, lights, light_of);
+        if (sc->n_lights > 0) {
+            st = upload(&sc->d_lights, lights.data(), lights.size() * sizeof(float));
+            if (st == HRT_OK) sc->allocs.push_back(sc->d_lights);
+            if (st == HRT_OK) st = upload(&sc->d_light_of, light_of.data(), light_of.size() * sizeof(int32_t));
+            if (st == HRT_OK) sc->allocs.push_back(sc->d_light_of);
+            if (st != HRT_OK) { hrt_scene_destroy(sc); return st; }
+        }
+    }
     for (uint32_t i = 0; i < f->n_prims; ++i)
         if (f->prims[i].kind == HRT_PRIM_MESH) {
             sc->mesh_prims.push_back((int)i);
@@ -2337,6 +2584,7 @@ hrt_status hrt_scene_stats(hrt_scene* sc, hrt_stats* stats) {
     stats->rays = c.rays; stats->samples = c.samples; stats->box_tests = c.box_tests; stats->tri_tests = c.tri_tests;
     stats->mesh_hits = c.mesh_hits; stats->env_lookups = c.env_lookups;
     stats->traversal_box_tests = c.trav_box_tests; stats->traversal_tri_tests = c.trav_tri_tests;
+    stats->shadow_rays = c.shadow_rays;
     stats->kernel_ms = sc->kernel_ms; stats->launches = sc->launches;
     stats->traversal_ms = sc->traversal_ms; stats->traversal_launches = sc->traversal_launches;
     sc->kernel_ms = 0.0; sc->launches = 0; sc->traversal_ms = 0.0; sc->traversal_launches = 0;
@@ -2780,6 +3028,7 @@ hrt_status hrt_multi_render(hrt_multi* m, const hrt_camera* cam, const hrt_param
             total.rays += one.rays; total.samples += one.samples; total.box_tests += one.box_tests; total.tri_tests += one.tri_tests;
             total.mesh_hits += one.mesh_hits; total.env_lookups += one.env_lookups; total.launches += one.launches;
             total.traversal_box_tests += one.traversal_box_tests; total.traversal_tri_tests += one.traversal_tri_tests;
+            total.shadow_rays += one.shadow_rays;
             total.traversal_launches += one.traversal_launches;
             if (one.kernel_ms > total.kernel_ms) total.kernel_ms = one.kernel_ms;          // the devices run side by side
             if (one.traversal_ms > total.traversal_ms) total.traversal_ms = one.traversal_ms;

@@ -12,6 +12,7 @@
 //     --dump-linear FILE.pfm (the fp32 linear film, bit for bit, next to the tonemapped image)
 //     --obj-indices reference|rebased (multi-object OBJ files: the reference's un-rebased face indices, mesh.cpp:111-114, or correct ones)
 //     --lens (thin-lens sampling with the scene's `aperture`: camera.h:34's commented-out circularRand(lensRadius); off = the reference)
+//     --nee (next-event estimation with MIS for the scene's rect and sphere lights; off = the reference's estimator)
 //     --no-progress (no reporter thread and no progress counter on the device: main.cpp:97-109), --progress-ms N (its interval, 500)
 //     --rccl (gather the film through an RCCL communicator even on one GPU; with --gpus N > 1 it always is)
 //     --adaptive T (adaptive sampling: a pixel stops once the relative standard error of its mean luminance is below T;
@@ -78,6 +79,7 @@ int main(int argc, char** argv) {
         else if (a == "--progress-ms") opt.progress_interval_ms = std::max(1, std::atoi(next("--progress-ms")));
         else if (a == "--rccl") opt.force_rccl = true;
         else if (a == "--lens") opt.thin_lens = true;
+        else if (a == "--nee") opt.nee = true;
         else if (a == "--obj-indices") { std::string v = next("--obj-indices"); setenv("HRT_OBJ_INDICES", v == "rebased" ? "rebased" : "reference", 1); }
         else if (a == "--bvh") {     // who builds the meshes' culling trees: the host (binned SAH, default) or the GPU (gpu-sah: the same tree; lbvh: fastest to build, +16 % box tests)
             const std::string v = next("--bvh");
@@ -157,11 +159,15 @@ int main(int argc, char** argv) {
                              12.0 * film->getFilm().width * film->getFilm().height;
         // wall_s: the reference's own stopwatch (main.cpp:144,184): process start to after the image file is written
         const double wall_s = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - start).count();
-        char extra[160] = "";
+        char extra[224] = "";
         if (opt.adaptive >= 0.0f) {   // the samples adaptive sampling took, and their share of the uniform render's
             const double uniform = (double)film->getFilm().width * film->getFilm().height * film->getFilm().samples;
             std::snprintf(extra, sizeof(extra), ", \"adaptive_threshold\": %g, \"samples_taken\": %llu, \"sample_fraction\": %.6f",
                           opt.adaptive, (unsigned long long)stats.samples, (double)stats.samples / uniform);
+        }
+        if (opt.nee) {                // the shadow rays of next-event estimation (not part of `rays`)
+            const size_t k = std::strlen(extra);
+            std::snprintf(extra + k, sizeof(extra) - k, ", \"shadow_rays\": %llu", (unsigned long long)stats.shadow_rays);
         }
         std::printf("{\"rays\": %llu, \"samples\": %llu, \"box_tests\": %llu, \"tri_tests\": %llu, \"render_s\": %.6f, "
                     "\"kernel_ms\": %.3f, \"mrays_per_s\": %.3f, \"msamples_per_s\": %.3f, \"algorithmic_gb_per_s\": %.3f, "

@@ -33,6 +33,9 @@ struct Checkpoint {
 };
 const char kMagic[8] = {'H', 'R', 'T', 'C', 'K', 'P', 'T', '2'};
 
+// A render with --nee folds this constant into its checkpoint's scene_hash: its sums are not the default estimator's, and a
+// checkpoint of the one cannot be continued by the other (the file format stays as it is).
+constexpr uint64_t kNeeHashSalt = 0x4e45452d4d495321ull;   // "NEE-MIS!"
 // FNV-1a over everything the kernels read of the scene (hrt_flat_scene's arrays) and the camera constants.
 uint64_t sceneHash(const hrt_flat_scene& f, const hrt_camera& cam) {
     uint64_t h = 1469598103934665603ull;
@@ -51,6 +54,12 @@ uint64_t sceneHash(const hrt_flat_scene& f, const hrt_camera& cam) {
     for (uint64_t i = 0; i < f.n_texels_f32; i += 61) mix(f.texels_f32 + i, sizeof(float));
     mix(&f.background_tex, sizeof(f.background_tex));
     return h;
+}
+
+// what a checkpoint's scene_hash holds: the scene and camera, and whether the render estimates with next-event estimation
+uint64_t renderHash(const hrt_flat_scene& f, const hrt_camera& cam, const RenderOptions& opt) {
+    const uint64_t h = sceneHash(f, cam);
+    return opt.nee ? h ^ kNeeHashSalt : h;
 }
 
 bool writeCheckpoint(const std::string& path, const Checkpoint& ck, const std::vector<float>& sums) {
@@ -108,6 +117,7 @@ hrt_status renderAdaptive(const hrt_flat_scene& flat, const hrt_camera& cam, hrt
         total.rays += ps.rays; total.samples += ps.samples; total.box_tests += ps.box_tests; total.tri_tests += ps.tri_tests;
         total.mesh_hits += ps.mesh_hits; total.env_lookups += ps.env_lookups; total.launches += ps.launches;
         total.traversal_box_tests += ps.traversal_box_tests; total.traversal_tri_tests += ps.traversal_tri_tests;
+        total.shadow_rays += ps.shadow_rays;
         total.kernel_ms += ps.kernel_ms;
         if (active == 0) break;
         if (opt.progress) std::cout << "\rPass " << pass << ": " << active << "/" << numPixels << " pixels active" << std::flush;
@@ -161,7 +171,8 @@ hrt_status render(int /*nThreads*/, const std::shared_ptr<Texture> background, c
     pr.width = f.width; pr.height = f.height; pr.samples = f.samples;
     pr.max_depth = opt.max_depth; pr.t_min = 0.001f; pr.quirks = opt.quirks;
     pr.seed_lo = (uint32_t)opt.seed; pr.seed_hi = (uint32_t)(opt.seed >> 32);
-    pr.flags = (opt.stats ? HRT_FLAG_STATS : 0) | (opt.thin_lens ? HRT_FLAG_THIN_LENS : 0) | (opt.progress ? HRT_FLAG_PROGRESS : 0);
+    pr.flags = (opt.stats ? HRT_FLAG_STATS : 0) | (opt.thin_lens ? HRT_FLAG_THIN_LENS : 0) | (opt.progress ? HRT_FLAG_PROGRESS : 0) |
+               (opt.nee ? HRT_FLAG_NEE : 0);
 
     if (opt.adaptive >= 0.0f) return renderAdaptive(flat, cam, pr, film, opt, stats, render_seconds);
 
@@ -219,7 +230,7 @@ hrt_status render(int /*nThreads*/, const std::shared_ptr<Texture> background, c
         std::string why;
         if (!readCheckpoint(opt.checkpoint, ck, sums, why)) { std::cerr << "\nresume: " << why << std::endl; cleanup(); return HRT_ERR_IO; }
         if (ck.width != f.width || ck.height != f.height || ck.samples != f.samples || ck.seed != opt.seed || ck.quirks != opt.quirks ||
-            ck.max_depth != opt.max_depth || ck.next_sample < 0 || ck.next_sample > f.samples || ck.scene_hash != sceneHash(flat, cam)) {
+            ck.max_depth != opt.max_depth || ck.next_sample < 0 || ck.next_sample > f.samples || ck.scene_hash != renderHash(flat, cam, opt)) {
             std::cerr << "\nresume: " << opt.checkpoint << " belongs to a different render (scene, camera, film, samples, seed, quirks or depth differ)" << std::endl;
             cleanup();
             return HRT_ERR_INVALID;
@@ -248,11 +259,12 @@ hrt_status render(int /*nThreads*/, const std::shared_ptr<Texture> background, c
         total.rays += ps.rays; total.samples += ps.samples; total.box_tests += ps.box_tests; total.tri_tests += ps.tri_tests;
         total.mesh_hits += ps.mesh_hits; total.env_lookups += ps.env_lookups; total.launches += ps.launches;
         total.traversal_box_tests += ps.traversal_box_tests; total.traversal_tri_tests += ps.traversal_tri_tests;
+        total.shadow_rays += ps.shadow_rays;
         total.kernel_ms += ps.kernel_ms;
         s_done += n;
         pathsBefore.store((long long)numPixels * (long long)s_done);
         if (!opt.checkpoint.empty()) {
-            Checkpoint ck{f.width, f.height, f.samples, s_done, opt.seed, opt.quirks, opt.max_depth, sceneHash(flat, cam)};
+            Checkpoint ck{f.width, f.height, f.samples, s_done, opt.seed, opt.quirks, opt.max_depth, renderHash(flat, cam, opt)};
             if (!writeCheckpoint(opt.checkpoint, ck, sums)) { std::cerr << "\ncannot write checkpoint " << opt.checkpoint << std::endl; cleanup(); return HRT_ERR_IO; }
         }
         if (s_done < f.samples) {   // preview: mean of the samples so far (the u8 film was resolved on the device)

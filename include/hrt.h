@@ -234,8 +234,15 @@ enum {
     HRT_FLAG_TIMING = 1u << 2, /* wavefront pipeline: also time the traversal kernel's launches with HIP events
                                   (hrt_stats.traversal_ms) */
     HRT_FLAG_THIN_LENS = 1u << 3, /* sample the lens as camera.h:34's commented-out call would (see hrt_camera); off = the reference */
-    HRT_FLAG_PROGRESS = 1u << 4 /* keep the host-readable progress counter of hrt_scene_progress / hrt_multi_progress up to date
+    HRT_FLAG_PROGRESS = 1u << 4, /* keep the host-readable progress counter of hrt_scene_progress / hrt_multi_progress up to date
                                     (the reference's reporter thread, main.cpp:97-109): one tiny launch per round */
+    HRT_FLAG_NEE = 1u << 5      /* next-event estimation (off = the reference's rayColour estimator): at every vertex whose
+                                    scatter is Lambertian and whose next segment is traced, one light of the scene's light table (its
+                                    unwrapped rects and spheres with a DiffuseLight material) is sampled and a shadow ray traced, and the
+                                    result is combined with the BSDF bounce by multiple importance sampling (power heuristic).  The path
+                                    itself, and hrt_stats::rays, are those of the default render; the shadow rays are counted in
+                                    hrt_stats::shadow_rays.  Wavefront pipeline only: with HRT_FLAG_MEGAKERNEL every render call returns
+                                    HRT_ERR_UNSUPPORTED.  A scene without table lights renders as without the flag. */
 };
 
 typedef struct hrt_rect { int32_t x0, y0, w, h; } hrt_rect;   /* y0 = row index from the TOP (pIdx / W) */
@@ -255,6 +262,7 @@ typedef struct hrt_stats {
     uint64_t traversal_launches;
     uint64_t traversal_box_tests, traversal_tri_tests;   /* the part of box_tests / tri_tests counted inside those k_wf_ext
                             launches (HRT_FLAG_STATS): rounds that run inside the task-persistent tail kernel are not in it */
+    uint64_t shadow_rays; /* HRT_FLAG_NEE: shadow rays traced (one per eligible vertex with a light sample); not part of `rays` */
 } hrt_stats;
 
 typedef struct hrt_hit {          /* hitRecord (hittable.h:8-25) as seen by rayColour */
