@@ -23,9 +23,11 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "hrt_device.h"
@@ -65,6 +67,33 @@ __host__ __device__ inline uint32_t fastdiv(uint32_t x, uint32_t d, uint64_t m) 
 #endif
 }
 inline uint64_t fastdiv_magic(uint32_t d) { return d <= 1 ? 0 : (uint64_t)(~0ull / d) + 1; }
+
+// The maps the host renders with (the partitions are validated by the caller).  Rect and stripe maps deal their pixels in
+// 8x8 tiles, the megakernel's work items.
+RenderMap rect_map(hrt_rect t) {
+    RenderMap map{};
+    map.mode = 0; map.x0 = t.x0; map.y0 = t.y0; map.rw = t.w; map.rh = t.h; map.R = 1; map.G = 1;
+    map.tiles_x = (map.rw + 7) / 8;
+    map.total_items = map.tiles_x * ((map.rh + 7) / 8) * 64;
+    map.m_rw = fastdiv_magic((uint32_t)map.rw); map.m_nl = fastdiv_magic((uint32_t)map.rw * (uint32_t)map.rh);
+    return map;
+}
+// the rows of the film `width` x `height` that rank `rank` of G owns in blocks of R (hrt_stripe_rows), in stripe order
+RenderMap stripe_map(int32_t width, int32_t height, int32_t R, int32_t rank, int32_t G) {
+    RenderMap map = rect_map({0, 0, width, hrt_stripe_rows(height, R, rank, G)});
+    map.mode = 1; map.R = R; map.rank = rank; map.G = G;
+    return map;
+}
+// the n pixels pix[0 .. n) of a stripe map's width x rows pixels (adaptive passes)
+RenderMap list_map(int32_t width, int32_t rows, int32_t R, int32_t rank, int32_t G, const int32_t* pix, uint32_t n) {
+    RenderMap map{};
+    map.mode = 2; map.R = R; map.rank = rank; map.G = G;
+    map.rw = width; map.rh = rows;
+    map.pix = pix; map.n_list = n;
+    map.total_items = (int32_t)n;
+    map.m_rw = fastdiv_magic((uint32_t)map.rw); map.m_nl = fastdiv_magic(n);
+    return map;
+}
 
 struct DeviceCounters {      // 64-bit accumulators in device memory
     unsigned long long rays, samples, box_tests, tri_tests, mesh_hits, env_lookups;
@@ -1555,14 +1584,40 @@ namespace {
         hipError_t _e = (expr);                              \
         if (_e != hipSuccess) return fail_hip(_e, #expr);    \
     } while (0)
+#define HRTCHK(expr)                                         \
+    do {                                                     \
+        hrt_status _s = (expr);                              \
+        if (_s != HRT_OK) return _s;                         \
+    } while (0)
 
-template <typename T>
-hrt_status upload(T** dptr, const void* src, size_t bytes) {
-    *dptr = nullptr;
-    size_t alloc = bytes ? bytes : 16;
-    hipError_t e = hipMalloc((void**)dptr, alloc);
-    if (e != hipSuccess) { g_err = std::string("hipMalloc: ") + hipGetErrorString(e); return e == hipErrorOutOfMemory ? HRT_ERR_OOM : HRT_ERR_HIP; }
-    if (bytes) HIPCHK(hipMemcpy(*dptr, src, bytes, hipMemcpyHostToDevice));
+// One hipMalloc allocation, freed when the buffer is destroyed or reset (on the device that is current then).
+class DevBuf {
+public:
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { reset(); p_ = o.p_; o.p_ = nullptr; } return *this; }
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { reset(); }
+    // replaces what the buffer holds by `bytes` of device memory; "<what>: <HIP error>" on failure
+    hrt_status alloc(size_t bytes, const char* what) {
+        reset();
+        hipError_t e = hipMalloc(&p_, bytes);
+        if (e == hipSuccess) return HRT_OK;
+        p_ = nullptr;
+        return fail(e == hipErrorOutOfMemory ? HRT_ERR_OOM : HRT_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    }
+    void reset() { if (p_) (void)hipFree(p_); p_ = nullptr; }
+    template <typename T = void> T* get() const { return static_cast<T*>(p_); }
+    explicit operator bool() const { return p_ != nullptr; }
+private:
+    void* p_ = nullptr;
+};
+
+// a device copy of `bytes` of host memory (an empty array gets 16 bytes, so that every table has an address)
+hrt_status upload(DevBuf& buf, const void* src, size_t bytes) {
+    HRTCHK(buf.alloc(bytes ? bytes : 16, "hipMalloc"));
+    if (bytes) HIPCHK(hipMemcpy(buf.get(), src, bytes, hipMemcpyHostToDevice));
     return HRT_OK;
 }
 
@@ -1570,7 +1625,7 @@ bool finite3(const float* p) { return p[0] == p[0] && p[1] == p[1] && p[2] == p[
 }  // namespace
 
 struct WfWorkspace {          // device workspace of the wavefront pipeline (grown on demand, kept with the scene)
-    void* base = nullptr;
+    DevBuf base;
     size_t bytes = 0;
     size_t slots = 0;
     int depth = 0, n_mesh = 0;
@@ -1582,7 +1637,7 @@ struct hrt_scene {
     int device = 0;
     int n_cus = 256;
     DScene ds{};
-    std::vector<void*> allocs;
+    std::vector<DevBuf> allocs;    // the uploaded tables, counters and light table that ds and the d_ pointers below point into
     std::vector<int> mesh_prims;   // indices of the HRT_PRIM_MESH entries of the world list, in list order
     std::vector<int> mesh_depths;  // BVH depth of each of them (selects the traversal kernel's stack size)
     int n_prims = 0;
@@ -1602,8 +1657,7 @@ struct hrt_scene {
     unsigned long long progress_base = 0;
     volatile unsigned long long progress_total = 0;
     // adaptive passes: the list of active pixels (ad_cap entries) and the block counts of its compaction (+ the total)
-    int32_t* d_ad_pix = nullptr;
-    unsigned* d_ad_blocks = nullptr;
+    DevBuf ad_pix, ad_blocks;
     size_t ad_cap = 0;
     // HRT_FLAG_NEE: the light table (hrt_device.h HRT_NEE_REC float4 per light) and the prim -> light map, built at hrt_scene_create
     float4* d_lights = nullptr;
@@ -1819,6 +1873,33 @@ hrt_status check_params(const hrt_params* p) {
     return HRT_OK;
 }
 
+hrt_status check_stripes(int32_t R, int32_t rank, int32_t G) {
+    if (R <= 0 || G <= 0 || rank < 0 || rank >= G) return fail(HRT_ERR_INVALID, "bad stripe partition");
+    return HRT_OK;
+}
+
+// blocks of 256 threads for a grid-stride loop over n items: one per 256 items, at most 8 per CU
+int grid_for(const hrt_scene* sc, long long n) { return (int)std::min<long long>((n + 255) / 256, (long long)sc->n_cus * 8); }
+
+// f(std::true_type{}) or f(std::false_type{}): a runtime flag as the template argument of the launch inside f
+template <typename F>
+void with_bool(bool b, F&& f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+
+// Stack depth variant of k_wf_ext / k_wf_tail for a BVH of `depth` levels (LDS per block grows with it) ...
+int depth_variant(int depth) { return depth <= 20 ? 20 : (depth <= 24 ? 24 : 32); }
+// ... and f(std::integral_constant<int, variant>{})
+template <typename F>
+void with_depth(int variant, F&& f) {
+    switch (variant) {
+        case 20: f(std::integral_constant<int, 20>{}); break;
+        case 24: f(std::integral_constant<int, 24>{}); break;
+        default: f(std::integral_constant<int, 32>{}); break;
+    }
+}
+
 hrt_status get_event(hrt_scene* sc, hipEvent_t* ev) {
     if (!sc->event_pool.empty()) { *ev = sc->event_pool.back(); sc->event_pool.pop_back(); return HRT_OK; }
     HIPCHK(hipEventCreate(ev));
@@ -1828,13 +1909,10 @@ hrt_status get_event(hrt_scene* sc, hipEvent_t* ev) {
 hrt_status launch_megakernel(hrt_scene* sc, const hrt_camera* cam, const hrt_params* pr, const RenderMap& map, float* d_out,
                              hipStream_t stream) {
     HIPCHK(hipMemsetAsync(sc->d_work, 0, sizeof(unsigned), stream));
-    int blocks = (map.total_items + HRT_BLOCK - 1) / HRT_BLOCK;
-    const int cap = sc->n_cus * 8;
-    if (blocks > cap) blocks = cap;
-    if (pr->flags & HRT_FLAG_STATS)
-        hipLaunchKernelGGL(k_pathtrace<true>, dim3(blocks), dim3(HRT_BLOCK), 0, stream, sc->ds, *cam, *pr, map, d_out, sc->d_counters, sc->d_work);
-    else
-        hipLaunchKernelGGL(k_pathtrace<false>, dim3(blocks), dim3(HRT_BLOCK), 0, stream, sc->ds, *cam, *pr, map, d_out, sc->d_counters, sc->d_work);
+    const int blocks = grid_for(sc, map.total_items);   // (of HRT_BLOCK = 256 threads)
+    with_bool(pr->flags & HRT_FLAG_STATS, [&](auto S) {
+        hipLaunchKernelGGL(k_pathtrace<decltype(S)::value>, dim3(blocks), dim3(HRT_BLOCK), 0, stream, sc->ds, *cam, *pr, map, d_out, sc->d_counters, sc->d_work);
+    });
     HIPCHK(hipGetLastError());
     return HRT_OK;
 }
@@ -1865,7 +1943,7 @@ hrt_status wf_reserve(hrt_scene* sc, size_t slots, int depth, bool nee) {
     WfWorkspace& w = sc->wf;
     const int n_mesh = (int)sc->mesh_prims.size();
     if (w.base && w.slots >= slots && w.depth >= depth && w.n_mesh == n_mesh && (w.nee || !nee)) return HRT_OK;
-    if (w.base) { HIPCHK(hipDeviceSynchronize()); (void)hipFree(w.base); w = WfWorkspace(); }
+    if (w.base) { HIPCHK(hipDeviceSynchronize()); w = WfWorkspace(); }
     const size_t max_tasks = slots / 64 + 1;   // the smallest task HRT_WF_TASK_SIZE can ask for is 64 positions (the default is >= 256)
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t f4 = al((slots + 4096) * sizeof(float4));   // to a whole number of tasks (T <= 4096): ref-walk records sit at the top of a task's segment
@@ -1875,10 +1953,9 @@ hrt_status wf_reserve(hrt_scene* sc, size_t slots, int depth, bool nee) {
     const size_t total = (sc->ds.stale_ff ? 12 : 11) * f4 + 2 * i4 + 3 * al(max_tasks * sizeof(unsigned)) + al(ctr_words * sizeof(unsigned)) + al(ref_cap * HRT_REF_GROUPS * sizeof(uint2)) +
                          al((size_t)sc->n_cus * 32 * sizeof(unsigned long long)) +                                     // 184 B per slot
                          (nee ? 3 * f4 + al((size_t)sc->n_cus * 32 * sizeof(unsigned long long)) : 0);                 // + 48 with NEE
-    void* base = nullptr;
-    hipError_t e = hipMalloc(&base, total);
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? HRT_ERR_OOM : HRT_ERR_HIP, std::string("hipMalloc(wavefront workspace): ") + hipGetErrorString(e));
-    char* p = (char*)base;
+    DevBuf base;
+    HRTCHK(base.alloc(total, "hipMalloc(wavefront workspace)"));
+    char* p = base.get<char>();
     auto take = [&](size_t bytes) { char* q = p; p += bytes; return q; };
     for (int k = 0; k < 2; ++k) {
         w.buf.S0[k] = (float4*)take(f4); w.buf.S1[k] = (float4*)take(f4); w.buf.S2[k] = (float4*)take(f4); w.buf.S3[k] = (float*)take(i4);
@@ -1900,7 +1977,7 @@ hrt_status wf_reserve(hrt_scene* sc, size_t slots, int depth, bool nee) {
         w.buf.wave_shadow = (unsigned long long*)take(al((size_t)w.buf.n_wave_rays * sizeof(unsigned long long)));
         HIPCHK(hipMemset(w.buf.wave_shadow, 0, (size_t)w.buf.n_wave_rays * sizeof(unsigned long long)));
     }
-    w.base = base; w.bytes = total; w.slots = slots; w.depth = depth; w.n_mesh = n_mesh; w.nee = nee;
+    w.base = std::move(base); w.bytes = total; w.slots = slots; w.depth = depth; w.n_mesh = n_mesh; w.nee = nee;
     return HRT_OK;
 }
 
@@ -2020,8 +2097,9 @@ hrt_status launch_wavefront(hrt_scene* sc, const hrt_camera* cam, const hrt_para
         if (nee) HIPCHK(hipMemsetAsync(w.direct, 0, (size_t)n_slots * sizeof(float4), stream));   // the shadow sums start at +0.0f
         next_counters((unsigned)task_blocks * 4u);
         w.ref_prod = ref_block(0, 0); w.ref_cons = ref_block(D, 0);
-        if (stats) hipLaunchKernelGGL(k_wf_gen<true>, dim3(task_blocks), dim3(256), 0, stream, sc->ds, *cam, *pr, map, ws, n_local, s0, n_slots, w, sc->d_counters);
-        else hipLaunchKernelGGL(k_wf_gen<false>, dim3(task_blocks), dim3(256), 0, stream, sc->ds, *cam, *pr, map, ws, n_local, s0, n_slots, w, sc->d_counters);
+        with_bool(stats, [&](auto S) {
+            hipLaunchKernelGGL(k_wf_gen<decltype(S)::value>, dim3(task_blocks), dim3(256), 0, stream, sc->ds, *cam, *pr, map, ws, n_local, s0, n_slots, w, sc->d_counters);
+        });
         for (int r = 0; r < tail_round; ++r) {
             const int par = r & 1;
             for (int m = 0; m < n_mesh; ++m) {
@@ -2030,21 +2108,21 @@ hrt_status launch_wavefront(hrt_scene* sc, const hrt_camera* cam, const hrt_para
                     const int p0 = sc->mesh_prims[m - 1] + 1;
                     next_counters((unsigned)task_blocks * 4u);
                     w.ref_prod = ref_block(r, m); w.ref_cons = ref_block(D, 0);
-                    if (stats) hipLaunchKernelGGL(k_wf_pre<true>, dim3(task_blocks), dim3(256), 0, stream, sc->ds, *pr, map, n_local, s0, r, par, p0, mp, w, sc->d_counters);
-                    else hipLaunchKernelGGL(k_wf_pre<false>, dim3(task_blocks), dim3(256), 0, stream, sc->ds, *pr, map, n_local, s0, r, par, p0, mp, w, sc->d_counters);
+                    with_bool(stats, [&](auto S) {
+                        hipLaunchKernelGGL(k_wf_pre<decltype(S)::value>, dim3(task_blocks), dim3(256), 0, stream, sc->ds, *pr, map, n_local, s0, r, par, p0, mp, w, sc->d_counters);
+                    });
                 }
                 hipEvent_t ea = nullptr, eb = nullptr;
-                if (timing) { st = get_event(sc, &ea); if (st != HRT_OK) return st; st = get_event(sc, &eb); if (st != HRT_OK) return st; HIPCHK(hipEventRecord(ea, stream)); }
+                if (timing) { HRTCHK(get_event(sc, &ea)); HRTCHK(get_event(sc, &eb)); HIPCHK(hipEventRecord(ea, stream)); }
                 // stack depth variant: LDS per block = DEPTH KB; resident blocks per CU: LDS 160 KB and 78 VGPRs -> 6 waves/SIMD
-                const int md = sc->mesh_depths[m];
-                const int variant = md <= 20 ? 20 : (md <= 24 ? 24 : 32);
+                const int variant = depth_variant(sc->mesh_depths[m]);
                 const int ext_blocks = sc->n_cus * (ext_per_cu_env ? ext_per_cu_env : (variant == 32 ? 4 : 6));
                 next_counters((unsigned)ext_blocks * (HRT_BLOCK / 64));
                 w.ref_prod = ref_block(D, 0); w.ref_cons = ref_block(r, m);
-#define HRT_LAUNCH_EXT(S, D) hipLaunchKernelGGL((k_wf_ext<S, D>), dim3(ext_blocks), dim3(HRT_BLOCK), 0, stream, sc->ds, *pr, mp, par, w, sc->d_counters, leaf_num)
-                if (stats) { if (variant == 20) HRT_LAUNCH_EXT(true, 20); else if (variant == 24) HRT_LAUNCH_EXT(true, 24); else HRT_LAUNCH_EXT(true, 32); }
-                else { if (variant == 20) HRT_LAUNCH_EXT(false, 20); else if (variant == 24) HRT_LAUNCH_EXT(false, 24); else HRT_LAUNCH_EXT(false, 32); }
-#undef HRT_LAUNCH_EXT
+                with_bool(stats, [&](auto S) { with_depth(variant, [&](auto DP) {
+                    hipLaunchKernelGGL((k_wf_ext<decltype(S)::value, decltype(DP)::value>), dim3(ext_blocks), dim3(HRT_BLOCK), 0, stream, sc->ds, *pr, mp, par, w,
+                                       sc->d_counters, leaf_num);
+                }); });
                 if (timing) { HIPCHK(hipEventRecord(eb, stream)); sc->pending_trav.push_back({ea, eb}); }
             }
             if (stale_ff) {
@@ -2053,16 +2131,15 @@ hrt_status launch_wavefront(hrt_scene* sc, const hrt_camera* cam, const hrt_para
             }
             next_counters((unsigned)task_blocks * 4u);
             w.ref_prod = ref_block(r + 1, 0); w.ref_cons = ref_block(D, 0);
-            if (nee) {
-                if (stats) hipLaunchKernelGGL((k_wf_shade<true, true>), dim3(task_blocks), dim3(256), 0, stream, sc->ds, *pr, map, ws, n_local, s0, r, w, sc->d_counters);
-                else hipLaunchKernelGGL((k_wf_shade<false, true>), dim3(task_blocks), dim3(256), 0, stream, sc->ds, *pr, map, ws, n_local, s0, r, w, sc->d_counters);
-                if (r + 1 < D) {   // survivors of the last round: none (bounce + 1 < max_depth)
-                    // (launches per round with NEE: pre + ext per mesh, stale, shade, shadow <= the 2 * max(1, n_mesh) + 2 of wf_counter_words)
-                    next_counters((unsigned)task_blocks * 4u);
-                    hipLaunchKernelGGL(k_wf_shadow, dim3(task_blocks), dim3(HRT_BLOCK), 0, stream, sc->ds, *pr, map, n_local, s0, r, w);
-                }
-            } else if (stats) hipLaunchKernelGGL((k_wf_shade<true, false>), dim3(task_blocks), dim3(256), 0, stream, sc->ds, *pr, map, ws, n_local, s0, r, w, sc->d_counters);
-            else hipLaunchKernelGGL((k_wf_shade<false, false>), dim3(task_blocks), dim3(256), 0, stream, sc->ds, *pr, map, ws, n_local, s0, r, w, sc->d_counters);
+            with_bool(nee, [&](auto N) { with_bool(stats, [&](auto S) {
+                hipLaunchKernelGGL((k_wf_shade<decltype(S)::value, decltype(N)::value>), dim3(task_blocks), dim3(256), 0, stream, sc->ds, *pr, map, ws, n_local, s0, r, w,
+                                   sc->d_counters);
+            }); });
+            if (nee && r + 1 < D) {   // survivors of the last round: none (bounce + 1 < max_depth)
+                // (launches per round with NEE: pre + ext per mesh, stale, shade, shadow <= the 2 * max(1, n_mesh) + 2 of wf_counter_words)
+                next_counters((unsigned)task_blocks * 4u);
+                hipLaunchKernelGGL(k_wf_shadow, dim3(task_blocks), dim3(HRT_BLOCK), 0, stream, sc->ds, *pr, map, n_local, s0, r, w);
+            }
             if (progress)   // paths ended so far = earlier batches + this batch's slots - the live ones (w.live, as k_wf_shade left it)
                 hipLaunchKernelGGL(k_wf_progress, dim3(1), dim3(256), 0, stream, w.live, w.n_tasks, sc->progress_base + n_slots, sc->d_progress);
         }
@@ -2071,16 +2148,16 @@ hrt_status launch_wavefront(hrt_scene* sc, const hrt_camera* cam, const hrt_para
             tm.n = n_mesh;
             int need = 0;
             for (int m = 0; m < n_mesh; ++m) { tm.prim[m] = sc->mesh_prims[m]; need = std::max(need, sc->mesh_depths[m]); }
-            const int variant = need <= 20 ? 20 : (need <= 24 ? 24 : 32);
+            const int variant = depth_variant(need);
             const int tail_blocks = (int)std::min<size_t>(((size_t)w.n_tasks + 3) / 4, (size_t)sc->n_cus * (variant == 32 ? 3 : 4));   // 38..50 KB of LDS per block
             next_counters((unsigned)tail_blocks * 4u);
             w.ref_prod = ref_block(D, 0); w.ref_cons = ref_block(D, 0);
-#define HRT_LAUNCH_TAIL(S, DP) hipLaunchKernelGGL((k_wf_tail<S, DP>), dim3(tail_blocks), dim3(256), 0, stream, sc->ds, *pr, map, ws, tm, n_local, s0, tail_round, D, w, sc->d_counters, leaf_num)
-            if (stats) { if (variant == 20) HRT_LAUNCH_TAIL(true, 20); else if (variant == 24) HRT_LAUNCH_TAIL(true, 24); else HRT_LAUNCH_TAIL(true, 32); }
-            else { if (variant == 20) HRT_LAUNCH_TAIL(false, 20); else if (variant == 24) HRT_LAUNCH_TAIL(false, 24); else HRT_LAUNCH_TAIL(false, 32); }
-#undef HRT_LAUNCH_TAIL
+            with_bool(stats, [&](auto S) { with_depth(variant, [&](auto DP) {
+                hipLaunchKernelGGL((k_wf_tail<decltype(S)::value, decltype(DP)::value>), dim3(tail_blocks), dim3(256), 0, stream, sc->ds, *pr, map, ws, tm, n_local, s0,
+                                   tail_round, D, w, sc->d_counters, leaf_num);
+            }); });
         }
-        const int rblocks = (int)std::min<size_t>((n_local + 255) / 256, (size_t)sc->n_cus * 8);
+        const int rblocks = grid_for(sc, n_local);
         if (map.mode == 2)
             hipLaunchKernelGGL(nee ? k_wf_reduce_list<true> : k_wf_reduce_list<false>, dim3(rblocks), dim3(256), 0, stream, w.rad, map.pix, n_local, c, s0 == 0 ? 1 : 0, s0 + c, d_out, d_sq, d_count,
                                sc->d_counters, w.wave_rays, w.n_wave_rays, (const float4*)w.direct, w.wave_shadow);
@@ -2110,14 +2187,11 @@ hrt_status launch_pathtrace(hrt_scene* sc, const hrt_camera* cam, const hrt_para
         sc->progress_total = (unsigned long long)map_pixels(map) * (unsigned long long)s_count;
     }
     hipEvent_t a, b;
-    hrt_status st = get_event(sc, &a);
-    if (st != HRT_OK) return st;
-    st = get_event(sc, &b);
-    if (st != HRT_OK) return st;
+    HRTCHK(get_event(sc, &a));
+    HRTCHK(get_event(sc, &b));
     HIPCHK(hipEventRecord(a, stream));
-    st = (pr->flags & HRT_FLAG_MEGAKERNEL) ? launch_megakernel(sc, cam, pr, map, d_out, stream)
-                                           : launch_wavefront(sc, cam, pr, map, d_out, stream, s_first, s_count, d_sq, d_count);
-    if (st != HRT_OK) return st;
+    HRTCHK((pr->flags & HRT_FLAG_MEGAKERNEL) ? launch_megakernel(sc, cam, pr, map, d_out, stream)
+                                             : launch_wavefront(sc, cam, pr, map, d_out, stream, s_first, s_count, d_sq, d_count));
     if (pr->flags & HRT_FLAG_PROGRESS) {   // whatever path rendered: everything has ended
         hipLaunchKernelGGL(k_set_progress, dim3(1), dim3(1), 0, stream, (unsigned long long)sc->progress_total, sc->d_progress);
         HIPCHK(hipGetLastError());
@@ -2128,24 +2202,57 @@ hrt_status launch_pathtrace(hrt_scene* sc, const hrt_camera* cam, const hrt_para
     return HRT_OK;
 }
 
+// adds the times of the event pairs in `list` to `ms` (and counts them in `*n`) and returns the events to the pool
+hrt_status fold_events(hrt_scene* sc, std::vector<hrt_scene::Pending>& list, double& ms_sum, uint64_t* n) {
+    for (auto& p : list) {
+        HIPCHK(hipEventSynchronize(p.b));
+        float ms = 0.0f;
+        HIPCHK(hipEventElapsedTime(&ms, p.a, p.b));
+        ms_sum += ms;
+        if (n) ++*n;
+        sc->event_pool.push_back(p.a); sc->event_pool.push_back(p.b);
+    }
+    list.clear();
+    return HRT_OK;
+}
 hrt_status fold_pending(hrt_scene* sc) {
-    for (auto& p : sc->pending) {
-        HIPCHK(hipEventSynchronize(p.b));
-        float ms = 0.0f;
-        HIPCHK(hipEventElapsedTime(&ms, p.a, p.b));
-        sc->kernel_ms += ms;
-        sc->event_pool.push_back(p.a); sc->event_pool.push_back(p.b);
+    HRTCHK(fold_events(sc, sc->pending, sc->kernel_ms, nullptr));
+    return fold_events(sc, sc->pending_trav, sc->traversal_ms, &sc->traversal_launches);
+}
+
+struct HostArray { void* host; size_t bytes; };
+
+// The body of the host-buffer render entry points, once they have validated every argument: discards the counters of
+// earlier asynchronous launches so that `stats` describes this call only, stages `arrays` back to back in one device
+// allocation (copied in if `copy_in`), calls run(dev, copy_out) with dev[k] the device copy of arrays[k], copies them back
+// unless run cleared copy_out, and reads the counters.  Arrays of 0 bytes in all (an empty share of stripes): run is not called.
+template <size_t N, typename Run>
+hrt_status render_via_host(hrt_scene* sc, hrt_stats* stats, const HostArray (&arrays)[N], bool copy_in, const char* what, Run run) {
+    HIPCHK(hipSetDevice(sc->device));
+    hrt_stats now;
+    HRTCHK(hrt_scene_stats(sc, &now));
+    size_t total = 0;
+    for (const HostArray& a : arrays) total += a.bytes;
+    if (total) {
+        DevBuf buf;
+        HRTCHK(buf.alloc(total, "hipMalloc"));
+        void* dev[N];
+        for (size_t k = 0, at = 0; k < N; at += arrays[k++].bytes) dev[k] = buf.get<char>() + at;
+        auto copy = [&](bool in) {
+            for (size_t k = 0; k < N; ++k) {
+                const hipError_t e = in ? hipMemcpy(dev[k], arrays[k].host, arrays[k].bytes, hipMemcpyHostToDevice)
+                                        : hipMemcpy(arrays[k].host, dev[k], arrays[k].bytes, hipMemcpyDeviceToHost);
+                if (e != hipSuccess) return fail_hip(e, (std::string(in ? "hipMemcpy H2D " : "hipMemcpy D2H ") + what).c_str());
+            }
+            return HRT_OK;
+        };
+        bool copy_out = true;
+        if (copy_in) HRTCHK(copy(true));
+        HRTCHK(run(dev, copy_out));
+        if (copy_out) HRTCHK(copy(false));
     }
-    sc->pending.clear();
-    for (auto& p : sc->pending_trav) {
-        HIPCHK(hipEventSynchronize(p.b));
-        float ms = 0.0f;
-        HIPCHK(hipEventElapsedTime(&ms, p.a, p.b));
-        sc->traversal_ms += ms;
-        sc->traversal_launches++;
-        sc->event_pool.push_back(p.a); sc->event_pool.push_back(p.b);
-    }
-    sc->pending_trav.clear();
+    HRTCHK(hrt_scene_stats(sc, &now));
+    if (stats) *stats = now;
     return HRT_OK;
 }
 
@@ -2212,20 +2319,15 @@ void hrt_scene_destroy(hrt_scene* sc) {
     for (auto& p : sc->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (auto& p : sc->pending_trav) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (hipEvent_t e : sc->event_pool) (void)hipEventDestroy(e);
-    if (sc->wf.base) (void)hipFree(sc->wf.base);
-    if (sc->d_ad_pix) (void)hipFree(sc->d_ad_pix);
-    if (sc->d_ad_blocks) (void)hipFree(sc->d_ad_blocks);
-    for (void* p : sc->allocs) (void)hipFree(p);
     if (sc->h_progress) (void)hipHostFree((void*)sc->h_progress);
-    delete sc;
+    delete sc;   // (and with it the device buffers)
 }
 
 hrt_status hrt_scene_create(const hrt_flat_scene* f, int device, hrt_scene** out) {
     HRT_API_TRY
     if (!out) return fail(HRT_ERR_INVALID, "out is NULL");
     *out = nullptr;
-    hrt_status st = validate(f);
-    if (st != HRT_OK) return st;
+    HRTCHK(validate(f));
     // the reference's own tree of every mesh, for the rays that must walk it (hrt_device.h ref_walk); part of the validation:
     // tri_ref_order must be the depth-first code of such a tree (checked before any device is touched)
     RefTree ref;
@@ -2241,23 +2343,24 @@ hrt_status hrt_scene_create(const hrt_flat_scene* f, int device, hrt_scene** out
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, device));
 
-    hrt_scene* sc = new (std::nothrow) hrt_scene;
+    // the scene is destroyed on every failure below, until *out takes it
+    std::unique_ptr<hrt_scene, decltype(&hrt_scene_destroy)> sc(new (std::nothrow) hrt_scene, hrt_scene_destroy);
     if (!sc) return fail(HRT_ERR_OOM, "host allocation failed");
     sc->device = device;
     sc->n_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-
-#define UP(dst, src, bytes)                                              \
-    do {                                                                 \
-        st = upload(&(dst), (src), (bytes));                             \
-        if (st != HRT_OK) { hrt_scene_destroy(sc); return st; }          \
-        sc->allocs.push_back((void*)(dst));                              \
-    } while (0)
+    auto up = [&](auto*& dst, const void* src, size_t bytes) {   // upload into a buffer the scene keeps
+        DevBuf b;
+        HRTCHK(upload(b, src, bytes));
+        dst = static_cast<std::remove_reference_t<decltype(dst)>>(b.get());
+        sc->allocs.push_back(std::move(b));
+        return HRT_OK;
+    };
 
     hrt_prim* d_prims; hrt_material* d_mats; hrt_texture* d_texs; hrt_mesh* d_meshes;
-    UP(d_prims, f->prims, sizeof(hrt_prim) * f->n_prims);
-    UP(d_mats, f->materials, sizeof(hrt_material) * f->n_materials);
-    UP(d_texs, f->textures, sizeof(hrt_texture) * f->n_textures);
-    UP(d_meshes, f->meshes, sizeof(hrt_mesh) * f->n_meshes);
+    HRTCHK(up(d_prims, f->prims, sizeof(hrt_prim) * f->n_prims));
+    HRTCHK(up(d_mats, f->materials, sizeof(hrt_material) * f->n_materials));
+    HRTCHK(up(d_texs, f->textures, sizeof(hrt_texture) * f->n_textures));
+    HRTCHK(up(d_meshes, f->meshes, sizeof(hrt_mesh) * f->n_meshes));
     // repack the BVH into 32-byte culling records and the triangles into 16-byte aligned records (hrt_pack.h)
     std::vector<uint32_t> qn;
     std::vector<float> grids;
@@ -2265,36 +2368,36 @@ hrt_status hrt_scene_create(const hrt_flat_scene* f, int device, hrt_scene** out
     if (const char* e = getenv("HRT_NODE_LAYOUT")) node_layout = strcmp(e, "treelet") == 0 ? 1 : 0;
     pack_nodes(f, qn, grids, node_layout);
     uint4* d_nodes; float4* d_grids;
-    UP(d_nodes, qn.data(), qn.size() * sizeof(uint32_t));
-    UP(d_grids, grids.data(), grids.size() * sizeof(float));
+    HRTCHK(up(d_nodes, qn.data(), qn.size() * sizeof(uint32_t)));
+    HRTCHK(up(d_grids, grids.data(), grids.size() * sizeof(float)));
     uint4 *d_rnodes, *d_rmesh; float4* d_rtris;
-    UP(d_rnodes, ref.nodes.data(), ref.nodes.size() * sizeof(uint32_t));
-    UP(d_rtris, ref.tris.data(), ref.tris.size() * sizeof(float));
-    UP(d_rmesh, ref.mesh_nodes.data(), ref.mesh_nodes.size() * sizeof(uint32_t));
+    HRTCHK(up(d_rnodes, ref.nodes.data(), ref.nodes.size() * sizeof(uint32_t)));
+    HRTCHK(up(d_rtris, ref.tris.data(), ref.tris.size() * sizeof(float)));
+    HRTCHK(up(d_rmesh, ref.mesh_nodes.data(), ref.mesh_nodes.size() * sizeof(uint32_t)));
     std::vector<float> pos, attr, box;
     pack_triangles(f, ref, pos, attr, box);
     float4 *d_pos, *d_attr, *d_box;
-    UP(d_pos, pos.data(), pos.size() * sizeof(float));
-    UP(d_attr, attr.data(), attr.size() * sizeof(float));
-    UP(d_box, box.data(), box.size() * sizeof(float));
+    HRTCHK(up(d_pos, pos.data(), pos.size() * sizeof(float)));
+    HRTCHK(up(d_attr, attr.data(), attr.size() * sizeof(float)));
+    HRTCHK(up(d_box, box.data(), box.size() * sizeof(float)));
     uint8_t* d_u8; float* d_f32;
-    UP(d_u8, f->texels_u8, (size_t)f->n_texels_u8);
-    UP(d_f32, f->texels_f32, (size_t)f->n_texels_f32 * sizeof(float));
-    DeviceCounters zero{};
-    UP(sc->d_counters, &zero, sizeof(zero));
-    unsigned zw = 0;
-    UP(sc->d_work, &zw, sizeof(zw));
-#undef UP
+    HRTCHK(up(d_u8, f->texels_u8, (size_t)f->n_texels_u8));
+    HRTCHK(up(d_f32, f->texels_f32, (size_t)f->n_texels_f32 * sizeof(float)));
+    const DeviceCounters zero{};
+    HRTCHK(up(sc->d_counters, &zero, sizeof(zero)));
+    const unsigned zw = 0;
+    HRTCHK(up(sc->d_work, &zw, sizeof(zw)));
     {   // the progress word: host memory the device can write and any host thread read without a HIP call (hrt_scene_progress);
         // made here, not at the first render, so that a reporter thread never sees the pointer change
         void* h = nullptr;
         e = hipHostMalloc(&h, 64, hipHostMallocMapped);
-        if (e != hipSuccess) { hrt_scene_destroy(sc); return fail_hip(e, "hipHostMalloc (progress counter)"); }
+        if (e != hipSuccess) return fail_hip(e, "hipHostMalloc (progress counter)");
         memset(h, 0, 64);
+        sc->h_progress = (volatile unsigned long long*)h;
         void* d = nullptr;
         e = hipHostGetDevicePointer(&d, h, 0);
-        if (e != hipSuccess) { (void)hipHostFree(h); hrt_scene_destroy(sc); return fail_hip(e, "hipHostGetDevicePointer"); }
-        sc->h_progress = (volatile unsigned long long*)h; sc->d_progress = (unsigned long long*)d;
+        if (e != hipSuccess) return fail_hip(e, "hipHostGetDevicePointer");
+        sc->d_progress = (unsigned long long*)d;
     }
 
     sc->ds.prims = d_prims; sc->ds.mats = d_mats; sc->ds.texs = d_texs; sc->ds.meshes = d_meshes;
@@ -2318,11 +2421,8 @@ hrt_status hrt_scene_create(const hrt_flat_scene* f, int device, hrt_scene** out
         std::vector<int32_t> light_of;
         sc->n_lights = build_light_table(f, lights, light_of);
         if (sc->n_lights > 0) {
-            st = upload(&sc->d_lights, lights.data(), lights.size() * sizeof(float));
-            if (st == HRT_OK) sc->allocs.push_back(sc->d_lights);
-            if (st == HRT_OK) st = upload(&sc->d_light_of, light_of.data(), light_of.size() * sizeof(int32_t));
-            if (st == HRT_OK) sc->allocs.push_back(sc->d_light_of);
-            if (st != HRT_OK) { hrt_scene_destroy(sc); return st; }
+            HRTCHK(up(sc->d_lights, lights.data(), lights.size() * sizeof(float)));
+            HRTCHK(up(sc->d_light_of, light_of.data(), light_of.size() * sizeof(int32_t)));
         }
     }
     for (uint32_t i = 0; i < f->n_prims; ++i)
@@ -2330,7 +2430,7 @@ hrt_status hrt_scene_create(const hrt_flat_scene* f, int device, hrt_scene** out
             sc->mesh_prims.push_back((int)i);
             sc->mesh_depths.push_back(bvh_depth(f, f->meshes[f->prims[i].mesh]));
         }
-    *out = sc;
+    *out = sc.release();
     return HRT_OK;
     HRT_API_CATCH
 }
@@ -2353,37 +2453,17 @@ int32_t hrt_stripe_row_index(int32_t height, int32_t R, int32_t rank, int32_t G,
 
 hrt_status hrt_render_stripes_device(hrt_scene* sc, const hrt_camera* cam, const hrt_params* pr, int32_t R, int32_t rank,
                                      int32_t G, float* d_out, void* stream) {
-    HRT_API_TRY
-    if (!sc || !cam || !d_out) return fail(HRT_ERR_INVALID, "NULL argument");
-    hrt_status st = check_params(pr);
-    if (st != HRT_OK) return st;
-    if (R <= 0 || G <= 0 || rank < 0 || rank >= G) return fail(HRT_ERR_INVALID, "bad stripe partition");
-    HIPCHK(hipSetDevice(sc->device));
-    RenderMap map{};
-    map.mode = 1; map.R = R; map.rank = rank; map.G = G;
-    map.rw = pr->width; map.rh = hrt_stripe_rows(pr->height, R, rank, G);
-    map.tiles_x = (map.rw + 7) / 8;
-    map.total_items = map.tiles_x * ((map.rh + 7) / 8) * 64;
-    map.m_rw = fastdiv_magic((uint32_t)map.rw); map.m_nl = fastdiv_magic((uint32_t)map.rw * (uint32_t)map.rh);
-    return launch_pathtrace(sc, cam, pr, map, d_out, (hipStream_t)stream);
-    HRT_API_CATCH
+    return hrt_render_stripes_accumulate_device(sc, cam, pr, R, rank, G, d_out, 0, -1, stream);
 }
 
 hrt_status hrt_render_stripes_accumulate_device(hrt_scene* sc, const hrt_camera* cam, const hrt_params* pr, int32_t R, int32_t rank,
                                                 int32_t G, float* d_accum, int32_t sample_first, int32_t sample_count, void* stream) {
     HRT_API_TRY
     if (!sc || !cam || !d_accum) return fail(HRT_ERR_INVALID, "NULL argument");
-    hrt_status st = check_params(pr);
-    if (st != HRT_OK) return st;
-    if (R <= 0 || G <= 0 || rank < 0 || rank >= G) return fail(HRT_ERR_INVALID, "bad stripe partition");
+    HRTCHK(check_params(pr));
+    HRTCHK(check_stripes(R, rank, G));
     HIPCHK(hipSetDevice(sc->device));
-    RenderMap map{};
-    map.mode = 1; map.R = R; map.rank = rank; map.G = G;
-    map.rw = pr->width; map.rh = hrt_stripe_rows(pr->height, R, rank, G);
-    map.tiles_x = (map.rw + 7) / 8;
-    map.total_items = map.tiles_x * ((map.rh + 7) / 8) * 64;
-    map.m_rw = fastdiv_magic((uint32_t)map.rw); map.m_nl = fastdiv_magic((uint32_t)map.rw * (uint32_t)map.rh);
-    return launch_pathtrace(sc, cam, pr, map, d_accum, (hipStream_t)stream, sample_first, sample_count);
+    return launch_pathtrace(sc, cam, pr, stripe_map(pr->width, pr->height, R, rank, G), d_accum, (hipStream_t)stream, sample_first, sample_count);
     HRT_API_CATCH
 }
 
@@ -2391,35 +2471,12 @@ hrt_status hrt_render_stripes_accumulate(hrt_scene* sc, const hrt_camera* cam, c
                                          float* accum, int32_t sample_first, int32_t sample_count, hrt_stats* stats) {
     HRT_API_TRY
     if (!sc || !cam || !accum) return fail(HRT_ERR_INVALID, "NULL argument");
-    hrt_status st = check_params(pr);
-    if (st != HRT_OK) return st;
-    if (R <= 0 || G <= 0 || rank < 0 || rank >= G) return fail(HRT_ERR_INVALID, "bad stripe partition");
-    HIPCHK(hipSetDevice(sc->device));
-    hrt_stats prev;
-    st = hrt_scene_stats(sc, &prev);
-    if (st != HRT_OK) return st;
+    HRTCHK(check_params(pr));
+    HRTCHK(check_stripes(R, rank, G));
     const size_t bytes = (size_t)hrt_stripe_rows(pr->height, R, rank, G) * pr->width * 3 * sizeof(float);
-    if (bytes) {
-        float* d = nullptr;
-        hipError_t e = hipMalloc((void**)&d, bytes);
-        if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? HRT_ERR_OOM : HRT_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
-        if (sample_first > 0) {
-            hipError_t e1 = hipMemcpy(d, accum, bytes, hipMemcpyHostToDevice);
-            if (e1 != hipSuccess) { (void)hipFree(d); return fail_hip(e1, "hipMemcpy H2D accumulation buffer"); }
-        }
-        st = hrt_render_stripes_accumulate_device(sc, cam, pr, R, rank, G, d, sample_first, sample_count, nullptr);
-        if (st == HRT_OK) {
-            hipError_t e2 = hipMemcpy(accum, d, bytes, hipMemcpyDeviceToHost);
-            if (e2 != hipSuccess) st = fail_hip(e2, "hipMemcpy D2H accumulation buffer");
-        }
-        (void)hipFree(d);
-        if (st != HRT_OK) return st;
-    }
-    hrt_stats now;
-    st = hrt_scene_stats(sc, &now);
-    if (st != HRT_OK) return st;
-    if (stats) *stats = now;
-    return HRT_OK;
+    return render_via_host(sc, stats, {{accum, bytes}}, sample_first > 0, "accumulation buffer", [&](void* const* d, bool&) {
+        return hrt_render_stripes_accumulate_device(sc, cam, pr, R, rank, G, (float*)d[0], sample_first, sample_count, nullptr);
+    });
     HRT_API_CATCH
 }
 
@@ -2427,9 +2484,8 @@ namespace {
 hrt_status check_adaptive(hrt_scene* sc, const hrt_camera* cam, const hrt_params* pr, int32_t R, int32_t rank, int32_t G, const hrt_adaptive* ad,
                           int32_t pass, int64_t* active_out) {
     if (!sc || !cam || !ad || !active_out) return fail(HRT_ERR_INVALID, "NULL argument");
-    hrt_status st = check_params(pr);
-    if (st != HRT_OK) return st;
-    if (R <= 0 || G <= 0 || rank < 0 || rank >= G) return fail(HRT_ERR_INVALID, "bad stripe partition");
+    HRTCHK(check_params(pr));
+    HRTCHK(check_stripes(R, rank, G));
     if (pr->flags & HRT_FLAG_MEGAKERNEL) return fail(HRT_ERR_UNSUPPORTED, "adaptive sampling renders on the wavefront pipeline only");
     if (ad->min_samples < 2 || ad->min_samples > pr->samples) return fail(HRT_ERR_INVALID, "min_samples must lie in [2, samples]");
     if (ad->pass_samples < 1) return fail(HRT_ERR_INVALID, "pass_samples must be >= 1");
@@ -2448,8 +2504,7 @@ hrt_status hrt_render_stripes_adaptive_device(hrt_scene* sc, const hrt_camera* c
                                               const hrt_adaptive* ad, float* d_sums, float* d_sq, int32_t* d_count, int32_t pass,
                                               int64_t* active_out, void* stream) {
     HRT_API_TRY
-    hrt_status st = check_adaptive(sc, cam, pr, R, rank, G, ad, pass, active_out);
-    if (st != HRT_OK) return st;
+    HRTCHK(check_adaptive(sc, cam, pr, R, rank, G, ad, pass, active_out));
     if (!d_sums || !d_sq || !d_count) return fail(HRT_ERR_INVALID, "NULL argument");
     *active_out = 0;
     const int64_t done = adaptive_done(pr, ad, pass);
@@ -2462,32 +2517,26 @@ hrt_status hrt_render_stripes_adaptive_device(hrt_scene* sc, const hrt_camera* c
     const unsigned n_blocks = (n_local + AD_ITEMS - 1) / AD_ITEMS;
     if (sc->ad_cap < n_local) {
         HIPCHK(hipDeviceSynchronize());       // an earlier pass may still read the list
-        if (sc->d_ad_pix) { (void)hipFree(sc->d_ad_pix); sc->d_ad_pix = nullptr; }
-        if (sc->d_ad_blocks) { (void)hipFree(sc->d_ad_blocks); sc->d_ad_blocks = nullptr; }
+        sc->ad_pix.reset(); sc->ad_blocks.reset();
         sc->ad_cap = 0;
-        hipError_t e = hipMalloc((void**)&sc->d_ad_pix, (size_t)n_local * sizeof(int32_t));
-        if (e == hipSuccess) e = hipMalloc((void**)&sc->d_ad_blocks, ((size_t)n_blocks + 1) * sizeof(unsigned));
-        if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? HRT_ERR_OOM : HRT_ERR_HIP, std::string("hipMalloc(adaptive list): ") + hipGetErrorString(e));
+        HRTCHK(sc->ad_pix.alloc((size_t)n_local * sizeof(int32_t), "hipMalloc(adaptive list)"));
+        HRTCHK(sc->ad_blocks.alloc(((size_t)n_blocks + 1) * sizeof(unsigned), "hipMalloc(adaptive list)"));
         sc->ad_cap = n_local;
     }
+    int32_t* const ad_pix = sc->ad_pix.get<int32_t>();
+    unsigned* const ad_blocks = sc->ad_blocks.get<unsigned>();
     AdRule rule{pass == 0 ? 1 : 0, (int)done, ad->min_samples, ad->threshold, ad->floor};
-    hipLaunchKernelGGL(k_ad_select<0>, dim3(n_blocks), dim3(256), 0, s, rule, d_sums, d_sq, d_count, n_local, sc->d_ad_blocks, sc->d_ad_pix);
-    hipLaunchKernelGGL(k_ad_scan, dim3(1), dim3(256), 0, s, sc->d_ad_blocks, n_blocks);
-    hipLaunchKernelGGL(k_ad_select<1>, dim3(n_blocks), dim3(256), 0, s, rule, d_sums, d_sq, d_count, n_local, sc->d_ad_blocks, sc->d_ad_pix);
+    hipLaunchKernelGGL(k_ad_select<0>, dim3(n_blocks), dim3(256), 0, s, rule, d_sums, d_sq, d_count, n_local, ad_blocks, ad_pix);
+    hipLaunchKernelGGL(k_ad_scan, dim3(1), dim3(256), 0, s, ad_blocks, n_blocks);
+    hipLaunchKernelGGL(k_ad_select<1>, dim3(n_blocks), dim3(256), 0, s, rule, d_sums, d_sq, d_count, n_local, ad_blocks, ad_pix);
     HIPCHK(hipGetLastError());
     unsigned n_active = 0;                    // the batch size: one 4-byte read-back per pass
-    HIPCHK(hipMemcpyAsync(&n_active, sc->d_ad_blocks + n_blocks, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&n_active, ad_blocks + n_blocks, sizeof(unsigned), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     if (n_active > n_local) return fail(HRT_ERR_HIP, "adaptive compaction produced more pixels than the stripes hold");
     *active_out = n_active;
     if (n_active == 0) return HRT_OK;
-    RenderMap map{};
-    map.mode = 2; map.R = R; map.rank = rank; map.G = G;
-    map.rw = pr->width; map.rh = rows;
-    map.pix = sc->d_ad_pix; map.n_list = n_active;
-    map.total_items = (int32_t)n_active;
-    map.m_rw = fastdiv_magic((uint32_t)map.rw); map.m_nl = fastdiv_magic(n_active);
-    return launch_pathtrace(sc, cam, pr, map, d_sums, s, (int)done, n_samples, d_sq, d_count);
+    return launch_pathtrace(sc, cam, pr, list_map(pr->width, rows, R, rank, G, ad_pix, n_active), d_sums, s, (int)done, n_samples, d_sq, d_count);
     HRT_API_CATCH
 }
 
@@ -2495,43 +2544,16 @@ hrt_status hrt_render_stripes_adaptive(hrt_scene* sc, const hrt_camera* cam, con
                                        const hrt_adaptive* ad, float* sums, float* sq, int32_t* count, int32_t pass, int64_t* active_out,
                                        hrt_stats* stats) {
     HRT_API_TRY
-    hrt_status st = check_adaptive(sc, cam, pr, R, rank, G, ad, pass, active_out);
-    if (st != HRT_OK) return st;
+    HRTCHK(check_adaptive(sc, cam, pr, R, rank, G, ad, pass, active_out));
     if (!sums || !sq || !count) return fail(HRT_ERR_INVALID, "NULL argument");
-    HIPCHK(hipSetDevice(sc->device));
-    hrt_stats prev;
-    st = hrt_scene_stats(sc, &prev);
-    if (st != HRT_OK) return st;
-    const size_t n = (size_t)hrt_stripe_rows(pr->height, R, rank, G) * pr->width;
     *active_out = 0;
-    if (n) {
-        const size_t b_sums = n * 3 * sizeof(float), b_sq = n * sizeof(float), b_cnt = n * sizeof(int32_t);
-        char* d = nullptr;
-        hipError_t e = hipMalloc((void**)&d, b_sums + b_sq + b_cnt);
-        if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? HRT_ERR_OOM : HRT_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
-        float* d_sums = (float*)d; float* d_sq = (float*)(d + b_sums); int32_t* d_cnt = (int32_t*)(d + b_sums + b_sq);
-        hipError_t e1 = hipSuccess;
-        if (pass > 0) {
-            e1 = hipMemcpy(d_sums, sums, b_sums, hipMemcpyHostToDevice);
-            if (e1 == hipSuccess) e1 = hipMemcpy(d_sq, sq, b_sq, hipMemcpyHostToDevice);
-            if (e1 == hipSuccess) e1 = hipMemcpy(d_cnt, count, b_cnt, hipMemcpyHostToDevice);
-        }
-        if (e1 != hipSuccess) st = fail_hip(e1, "hipMemcpy H2D adaptive buffers");
-        else st = hrt_render_stripes_adaptive_device(sc, cam, pr, R, rank, G, ad, d_sums, d_sq, d_cnt, pass, active_out, nullptr);
-        if (st == HRT_OK && (pass == 0 || *active_out > 0)) {
-            hipError_t e2 = hipMemcpy(sums, d_sums, b_sums, hipMemcpyDeviceToHost);
-            if (e2 == hipSuccess) e2 = hipMemcpy(sq, d_sq, b_sq, hipMemcpyDeviceToHost);
-            if (e2 == hipSuccess) e2 = hipMemcpy(count, d_cnt, b_cnt, hipMemcpyDeviceToHost);
-            if (e2 != hipSuccess) st = fail_hip(e2, "hipMemcpy D2H adaptive buffers");
-        }
-        (void)hipFree(d);
-        if (st != HRT_OK) return st;
-    }
-    hrt_stats now;
-    st = hrt_scene_stats(sc, &now);
-    if (st != HRT_OK) return st;
-    if (stats) *stats = now;
-    return HRT_OK;
+    const size_t n = (size_t)hrt_stripe_rows(pr->height, R, rank, G) * pr->width;
+    const HostArray arrays[] = {{sums, n * 3 * sizeof(float)}, {sq, n * sizeof(float)}, {count, n * sizeof(int32_t)}};
+    return render_via_host(sc, stats, arrays, pass > 0, "adaptive buffers", [&](void* const* d, bool& copy_out) {
+        HRTCHK(hrt_render_stripes_adaptive_device(sc, cam, pr, R, rank, G, ad, (float*)d[0], (float*)d[1], (int32_t*)d[2], pass, active_out, nullptr));
+        copy_out = pass == 0 || *active_out > 0;
+        return HRT_OK;
+    });
     HRT_API_CATCH
 }
 
@@ -2540,8 +2562,7 @@ hrt_status hrt_adaptive_mean_device(hrt_scene* sc, const float* d_sums, const in
     if (!sc || !d_sums || !d_count || !d_mean || n_pixels < 0) return fail(HRT_ERR_INVALID, "bad argument");
     if (n_pixels == 0) return HRT_OK;
     HIPCHK(hipSetDevice(sc->device));
-    const int blocks = (int)std::min<int64_t>((n_pixels + 255) / 256, (int64_t)sc->n_cus * 8);
-    hipLaunchKernelGGL(k_ad_mean, dim3(blocks), dim3(256), 0, (hipStream_t)stream, d_sums, d_count, (long long)n_pixels, d_mean);
+    hipLaunchKernelGGL(k_ad_mean, dim3(grid_for(sc, n_pixels)), dim3(256), 0, (hipStream_t)stream, d_sums, d_count, (long long)n_pixels, d_mean);
     HIPCHK(hipGetLastError());
     return HRT_OK;
     HRT_API_CATCH
@@ -2552,8 +2573,7 @@ hrt_status hrt_scene_stats(hrt_scene* sc, hrt_stats* stats) {
     if (!sc || !stats) return fail(HRT_ERR_INVALID, "NULL argument");
     HIPCHK(hipSetDevice(sc->device));
     HIPCHK(hipDeviceSynchronize());
-    hrt_status st = fold_pending(sc);
-    if (st != HRT_OK) return st;
+    HRTCHK(fold_pending(sc));
     DeviceCounters c;
     HIPCHK(hipMemcpy(&c, sc->d_counters, sizeof(c), hipMemcpyDeviceToHost));
     HIPCHK(hipMemset(sc->d_counters, 0, sizeof(c)));
@@ -2596,36 +2616,13 @@ hrt_status hrt_render_tile(hrt_scene* sc, const hrt_camera* cam, const hrt_param
                            hrt_stats* stats) {
     HRT_API_TRY
     if (!sc || !cam || !out) return fail(HRT_ERR_INVALID, "NULL argument");
-    hrt_status st = check_params(pr);
-    if (st != HRT_OK) return st;
+    HRTCHK(check_params(pr));
     if (tile.w <= 0 || tile.h <= 0 || tile.x0 < 0 || tile.y0 < 0 || tile.x0 + tile.w > pr->width || tile.y0 + tile.h > pr->height)
         return fail(HRT_ERR_INVALID, "tile outside the film");
-    HIPCHK(hipSetDevice(sc->device));
-    // discard counters of earlier async launches so `stats` describes this call only
-    hrt_stats prev;
-    st = hrt_scene_stats(sc, &prev);
-    if (st != HRT_OK) return st;
     const size_t bytes = (size_t)tile.w * tile.h * 3 * sizeof(float);
-    float* d_out = nullptr;
-    hipError_t e = hipMalloc((void**)&d_out, bytes);
-    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? HRT_ERR_OOM : HRT_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
-    RenderMap map{};
-    map.mode = 0; map.x0 = tile.x0; map.y0 = tile.y0; map.rw = tile.w; map.rh = tile.h; map.R = 1; map.G = 1;
-    map.tiles_x = (map.rw + 7) / 8;
-    map.total_items = map.tiles_x * ((map.rh + 7) / 8) * 64;
-    map.m_rw = fastdiv_magic((uint32_t)map.rw); map.m_nl = fastdiv_magic((uint32_t)map.rw * (uint32_t)map.rh);
-    st = launch_pathtrace(sc, cam, pr, map, d_out, nullptr);
-    if (st == HRT_OK) {
-        e = hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) st = fail_hip(e, "hipMemcpy D2H film tile");
-    }
-    (void)hipFree(d_out);
-    if (st != HRT_OK) return st;
-    hrt_stats now;
-    st = hrt_scene_stats(sc, &now);
-    if (st != HRT_OK) return st;
-    if (stats) *stats = now;
-    return HRT_OK;
+    return render_via_host(sc, stats, {{out, bytes}}, false, "film tile", [&](void* const* d, bool&) {
+        return launch_pathtrace(sc, cam, pr, rect_map(tile), (float*)d[0], nullptr);
+    });
     HRT_API_CATCH
 }
 
@@ -2633,32 +2630,12 @@ hrt_status hrt_render_stripes(hrt_scene* sc, const hrt_camera* cam, const hrt_pa
                               float* out, hrt_stats* stats) {
     HRT_API_TRY
     if (!sc || !cam || !out) return fail(HRT_ERR_INVALID, "NULL argument");
-    hrt_status st = check_params(pr);
-    if (st != HRT_OK) return st;
-    HIPCHK(hipSetDevice(sc->device));
-    hrt_stats prev;
-    st = hrt_scene_stats(sc, &prev);
-    if (st != HRT_OK) return st;
-    const int32_t rows = hrt_stripe_rows(pr->height, R, rank, G);
-    if (R <= 0 || G <= 0 || rank < 0 || rank >= G) return fail(HRT_ERR_INVALID, "bad stripe partition");
-    const size_t bytes = (size_t)rows * pr->width * 3 * sizeof(float);
-    float* d_out = nullptr;
-    if (bytes) {
-        hipError_t e = hipMalloc((void**)&d_out, bytes);
-        if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? HRT_ERR_OOM : HRT_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
-        st = hrt_render_stripes_device(sc, cam, pr, R, rank, G, d_out, nullptr);
-        if (st == HRT_OK) {
-            hipError_t e2 = hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost);
-            if (e2 != hipSuccess) st = fail_hip(e2, "hipMemcpy D2H film stripes");
-        }
-        (void)hipFree(d_out);
-        if (st != HRT_OK) return st;
-    }
-    hrt_stats now;
-    st = hrt_scene_stats(sc, &now);
-    if (st != HRT_OK) return st;
-    if (stats) *stats = now;
-    return HRT_OK;
+    HRTCHK(check_params(pr));
+    HRTCHK(check_stripes(R, rank, G));
+    const size_t bytes = (size_t)hrt_stripe_rows(pr->height, R, rank, G) * pr->width * 3 * sizeof(float);
+    return render_via_host(sc, stats, {{out, bytes}}, false, "film stripes", [&](void* const* d, bool&) {
+        return hrt_render_stripes_device(sc, cam, pr, R, rank, G, (float*)d[0], nullptr);
+    });
     HRT_API_CATCH
 }
 
@@ -2667,9 +2644,7 @@ hrt_status hrt_resolve_u8_device(hrt_scene* sc, const float* d_rgb, int64_t n_pi
     if (!sc || !d_rgb || !d_out || n_pixels < 0) return fail(HRT_ERR_INVALID, "bad argument");
     if (n_pixels == 0) return HRT_OK;
     HIPCHK(hipSetDevice(sc->device));
-    int blocks = (int)((n_pixels + 255) / 256);
-    if (blocks > sc->n_cus * 8) blocks = sc->n_cus * 8;
-    hipLaunchKernelGGL(k_resolve, dim3(blocks), dim3(256), 0, (hipStream_t)stream, d_rgb, (long long)n_pixels, d_out);
+    hipLaunchKernelGGL(k_resolve, dim3(grid_for(sc, n_pixels)), dim3(256), 0, (hipStream_t)stream, d_rgb, (long long)n_pixels, d_out);
     HIPCHK(hipGetLastError());
     return HRT_OK;
     HRT_API_CATCH
@@ -2680,17 +2655,14 @@ hrt_status hrt_resolve_u8(hrt_scene* sc, const float* rgb, int64_t n_pixels, uin
     if (!sc || !rgb || !out || n_pixels < 0) return fail(HRT_ERR_INVALID, "bad argument");
     if (n_pixels == 0) return HRT_OK;
     HIPCHK(hipSetDevice(sc->device));
-    float* d_in = nullptr; uint8_t* d_out = nullptr;
-    HIPCHK(hipMalloc((void**)&d_in, (size_t)n_pixels * 12));
-    hipError_t e = hipMalloc((void**)&d_out, (size_t)n_pixels * 3);
-    if (e != hipSuccess) { (void)hipFree(d_in); return fail_hip(e, "hipMalloc"); }
-    hrt_status st = HRT_OK;
-    e = hipMemcpy(d_in, rgb, (size_t)n_pixels * 12, hipMemcpyHostToDevice);
-    if (e != hipSuccess) st = fail_hip(e, "hipMemcpy H2D");
-    if (st == HRT_OK) st = hrt_resolve_u8_device(sc, d_in, n_pixels, d_out, nullptr);
-    if (st == HRT_OK) { e = hipMemcpy(out, d_out, (size_t)n_pixels * 3, hipMemcpyDeviceToHost); if (e != hipSuccess) st = fail_hip(e, "hipMemcpy D2H"); }
-    (void)hipFree(d_in); (void)hipFree(d_out);
-    return st;
+    DevBuf d_in, d_out;
+    HRTCHK(d_in.alloc((size_t)n_pixels * 12, "hipMalloc"));
+    HRTCHK(d_out.alloc((size_t)n_pixels * 3, "hipMalloc"));
+    hipError_t e = hipMemcpy(d_in.get(), rgb, (size_t)n_pixels * 12, hipMemcpyHostToDevice);
+    if (e != hipSuccess) return fail_hip(e, "hipMemcpy H2D");
+    HRTCHK(hrt_resolve_u8_device(sc, d_in.get<float>(), n_pixels, d_out.get<uint8_t>(), nullptr));
+    e = hipMemcpy(out, d_out.get(), (size_t)n_pixels * 3, hipMemcpyDeviceToHost);
+    return e == hipSuccess ? HRT_OK : fail_hip(e, "hipMemcpy D2H");
     HRT_API_CATCH
 }
 
@@ -2700,22 +2672,19 @@ hrt_status hrt_closest_hit(hrt_scene* sc, const hrt_params* pr, int64_t n, const
     if (!sc || !pr || !o || !d || !out || n < 0) return fail(HRT_ERR_INVALID, "bad argument");
     if (n == 0) return HRT_OK;
     HIPCHK(hipSetDevice(sc->device));
-    float *d_o = nullptr, *d_d = nullptr; hrt_hit* d_h = nullptr;
-    hrt_status st = HRT_OK;
+    DevBuf d_o, d_d, d_h;
+    HRTCHK(d_o.alloc((size_t)n * 12, "hipMalloc"));
+    HRTCHK(d_d.alloc((size_t)n * 12, "hipMalloc"));
+    HRTCHK(d_h.alloc((size_t)n * sizeof(hrt_hit), "hipMalloc"));
     hipError_t e;
-    if ((e = hipMalloc((void**)&d_o, (size_t)n * 12)) != hipSuccess) st = fail_hip(e, "hipMalloc");
-    if (st == HRT_OK && (e = hipMalloc((void**)&d_d, (size_t)n * 12)) != hipSuccess) st = fail_hip(e, "hipMalloc");
-    if (st == HRT_OK && (e = hipMalloc((void**)&d_h, (size_t)n * sizeof(hrt_hit))) != hipSuccess) st = fail_hip(e, "hipMalloc");
-    if (st == HRT_OK && (e = hipMemcpy(d_o, o, (size_t)n * 12, hipMemcpyHostToDevice)) != hipSuccess) st = fail_hip(e, "hipMemcpy");
-    if (st == HRT_OK && (e = hipMemcpy(d_d, d, (size_t)n * 12, hipMemcpyHostToDevice)) != hipSuccess) st = fail_hip(e, "hipMemcpy");
-    if (st == HRT_OK) {
-        const int blocks = (int)((n + HRT_BLOCK - 1) / HRT_BLOCK);
-        hipLaunchKernelGGL(k_closest_hit, dim3(blocks), dim3(HRT_BLOCK), 0, 0, sc->ds, *pr, (long long)n, d_o, d_d, t_min, t_max, pixel0, d_h);
-        if ((e = hipGetLastError()) != hipSuccess) st = fail_hip(e, "k_closest_hit launch");
-    }
-    if (st == HRT_OK && (e = hipMemcpy(out, d_h, (size_t)n * sizeof(hrt_hit), hipMemcpyDeviceToHost)) != hipSuccess) st = fail_hip(e, "hipMemcpy D2H");
-    (void)hipFree(d_o); (void)hipFree(d_d); (void)hipFree(d_h);
-    return st;
+    if ((e = hipMemcpy(d_o.get(), o, (size_t)n * 12, hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "hipMemcpy");
+    if ((e = hipMemcpy(d_d.get(), d, (size_t)n * 12, hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "hipMemcpy");
+    const int blocks = (int)((n + HRT_BLOCK - 1) / HRT_BLOCK);
+    hipLaunchKernelGGL(k_closest_hit, dim3(blocks), dim3(HRT_BLOCK), 0, 0, sc->ds, *pr, (long long)n, d_o.get<float>(), d_d.get<float>(), t_min, t_max, pixel0,
+                       d_h.get<hrt_hit>());
+    if ((e = hipGetLastError()) != hipSuccess) return fail_hip(e, "k_closest_hit launch");
+    if ((e = hipMemcpy(out, d_h.get(), (size_t)n * sizeof(hrt_hit), hipMemcpyDeviceToHost)) != hipSuccess) return fail_hip(e, "hipMemcpy D2H");
+    return HRT_OK;
     HRT_API_CATCH
 }
 
@@ -2726,20 +2695,17 @@ hrt_status hrt_math_probe(int device, int32_t op, int64_t n, const float* in, co
     if (n == 0) return HRT_OK;
     HIPCHK(hipSetDevice(device));
     const size_t n_in = (size_t)n * (op == 5 ? 4 : 1), n_in2 = (size_t)n * (op == 5 ? 2 : 1), n_out = (size_t)n * (op == 5 ? 4 : 1);
-    float *d_in = nullptr, *d_in2 = nullptr, *d_out = nullptr;
-    hrt_status st = HRT_OK; hipError_t e;
-    if ((e = hipMalloc((void**)&d_in, n_in * 4)) != hipSuccess) st = fail_hip(e, "hipMalloc");
-    if (st == HRT_OK && (e = hipMalloc((void**)&d_in2, n_in2 * 4)) != hipSuccess) st = fail_hip(e, "hipMalloc");
-    if (st == HRT_OK && (e = hipMalloc((void**)&d_out, n_out * 4)) != hipSuccess) st = fail_hip(e, "hipMalloc");
-    if (st == HRT_OK && (e = hipMemcpy(d_in, in, n_in * 4, hipMemcpyHostToDevice)) != hipSuccess) st = fail_hip(e, "hipMemcpy");
-    if (st == HRT_OK && in2 && (e = hipMemcpy(d_in2, in2, n_in2 * 4, hipMemcpyHostToDevice)) != hipSuccess) st = fail_hip(e, "hipMemcpy");
-    if (st == HRT_OK) {
-        hipLaunchKernelGGL(k_math_probe, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, op, (long long)n, d_in, d_in2, d_out);
-        if ((e = hipGetLastError()) != hipSuccess) st = fail_hip(e, "k_math_probe launch");
-    }
-    if (st == HRT_OK && (e = hipMemcpy(out, d_out, n_out * 4, hipMemcpyDeviceToHost)) != hipSuccess) st = fail_hip(e, "hipMemcpy D2H");
-    (void)hipFree(d_in); (void)hipFree(d_in2); (void)hipFree(d_out);
-    return st;
+    DevBuf d_in, d_in2, d_out;
+    HRTCHK(d_in.alloc(n_in * 4, "hipMalloc"));
+    HRTCHK(d_in2.alloc(n_in2 * 4, "hipMalloc"));
+    HRTCHK(d_out.alloc(n_out * 4, "hipMalloc"));
+    hipError_t e;
+    if ((e = hipMemcpy(d_in.get(), in, n_in * 4, hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "hipMemcpy");
+    if (in2 && (e = hipMemcpy(d_in2.get(), in2, n_in2 * 4, hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "hipMemcpy");
+    hipLaunchKernelGGL(k_math_probe, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, op, (long long)n, d_in.get<float>(), d_in2.get<float>(), d_out.get<float>());
+    if ((e = hipGetLastError()) != hipSuccess) return fail_hip(e, "k_math_probe launch");
+    if ((e = hipMemcpy(out, d_out.get(), n_out * 4, hipMemcpyDeviceToHost)) != hipSuccess) return fail_hip(e, "hipMemcpy D2H");
+    return HRT_OK;
     HRT_API_CATCH
 }
 
@@ -2751,11 +2717,12 @@ struct hrt_multi {
     std::vector<hrt_scene*> scenes;
     std::vector<hipStream_t> streams;
     std::vector<ncclComm_t> comms;       // empty until the first gather that needs them
-    std::vector<float*> d_accum;         // per rank: `share` floats (its stripes, padded to the largest share)
-    std::vector<float*> d_gather;        // per rank: G x share floats (ncclAllGather's receive buffer)
-    float* d_film = nullptr;             // first device: H x W x 3 sums in film order
-    float* d_mean = nullptr;             // first device: preview means
-    uint8_t* d_u8 = nullptr;
+    std::vector<DevBuf> d_accum;         // per rank: `share` floats (its stripes, padded to the largest share)
+    std::vector<DevBuf> d_gather;        // per rank: G x share floats (ncclAllGather's receive buffer; loopback: the first rank's)
+    float* gathered = nullptr;           // first device: the gathered stripes (d_gather[0], or with one rank and no communicator d_accum[0])
+    DevBuf d_film;                       // first device: H x W x 3 sums in film order
+    DevBuf d_mean;                       // first device: preview means
+    DevBuf d_u8;
     int W = 0, H = 0, R = 0;
     long long share = 0;
     bool use_rccl = false;
@@ -2806,18 +2773,26 @@ hrt_status fail_nccl(ncclResult_t r, const char* what) { g_err = std::string(wha
 #define NCCLCHK(expr) do { ncclResult_t _r = (expr); if (_r != ncclSuccess) return fail_nccl(_r, #expr); } while (0)
 
 void multi_free_buffers(hrt_multi* m) {
+    m->gathered = nullptr;
     for (size_t g = 0; g < m->devices.size(); ++g) {
         (void)hipSetDevice(m->devices[g]);
-        if (g < m->d_gather.size() && m->d_gather[g] && (g >= m->d_accum.size() || m->d_gather[g] != m->d_accum[g])) (void)hipFree(m->d_gather[g]);
-        if (g < m->d_accum.size() && m->d_accum[g]) (void)hipFree(m->d_accum[g]);
+        if (g < m->d_gather.size()) m->d_gather[g].reset();
+        if (g < m->d_accum.size()) m->d_accum[g].reset();
     }
     m->d_accum.clear(); m->d_gather.clear();
     if (!m->devices.empty()) (void)hipSetDevice(m->devices[0]);
-    if (m->d_film) (void)hipFree(m->d_film);
-    if (m->d_mean) (void)hipFree(m->d_mean);
-    if (m->d_u8) (void)hipFree(m->d_u8);
-    m->d_film = m->d_mean = nullptr; m->d_u8 = nullptr;
+    m->d_film.reset(); m->d_mean.reset(); m->d_u8.reset();
     m->W = m->H = m->R = 0; m->share = 0;
+}
+// adds one device's counters to a session's total: counts add up, times are the slowest device's (the devices run side by side)
+void add_stats(hrt_stats& total, const hrt_stats& one) {
+    total.rays += one.rays; total.samples += one.samples; total.box_tests += one.box_tests; total.tri_tests += one.tri_tests;
+    total.mesh_hits += one.mesh_hits; total.env_lookups += one.env_lookups; total.launches += one.launches;
+    total.traversal_box_tests += one.traversal_box_tests; total.traversal_tri_tests += one.traversal_tri_tests;
+    total.shadow_rays += one.shadow_rays;
+    total.traversal_launches += one.traversal_launches;
+    total.kernel_ms = std::max(total.kernel_ms, one.kernel_ms);
+    total.traversal_ms = std::max(total.traversal_ms, one.traversal_ms);
 }
 hrt_status multi_reserve(hrt_multi* m, int W, int H, int R) {
     if (m->W == W && m->H == H && m->R == R && !m->d_accum.empty()) return HRT_OK;
@@ -2825,18 +2800,19 @@ hrt_status multi_reserve(hrt_multi* m, int W, int H, int R) {
     const int G = (int)m->devices.size();
     m->share = (long long)hrt_stripe_rows(H, R, 0, G) * W * 3;        // rank 0 owns the most rows
     if (m->share == 0) m->share = 4;
-    m->d_accum.assign(G, nullptr); m->d_gather.assign(G, nullptr);
+    m->d_accum.resize(G); m->d_gather.resize(G);
     for (int g = 0; g < G; ++g) {
         HIPCHK(hipSetDevice(m->devices[g]));
-        HIPCHK(hipMalloc((void**)&m->d_accum[g], (size_t)m->share * sizeof(float)));
-        HIPCHK(hipMemset(m->d_accum[g], 0, (size_t)m->share * sizeof(float)));
-        if (m->use_rccl || (m->loopback && g == 0 && G > 1)) HIPCHK(hipMalloc((void**)&m->d_gather[g], (size_t)m->share * G * sizeof(float)));
+        HRTCHK(m->d_accum[g].alloc((size_t)m->share * sizeof(float), "hipMalloc"));
+        HIPCHK(hipMemset(m->d_accum[g].get(), 0, (size_t)m->share * sizeof(float)));
+        if (m->use_rccl || (m->loopback && g == 0 && G > 1)) HRTCHK(m->d_gather[g].alloc((size_t)m->share * G * sizeof(float), "hipMalloc"));
     }
-    if (!m->d_gather[0]) m->d_gather[0] = m->d_accum[0];               // one rank, no communicator: its stripes ARE the gathered buffer
+    // (one rank, no communicator: its stripes ARE the gathered buffer)
+    m->gathered = m->d_gather[0] ? m->d_gather[0].get<float>() : m->d_accum[0].get<float>();
     HIPCHK(hipSetDevice(m->devices[0]));
-    HIPCHK(hipMalloc((void**)&m->d_film, (size_t)W * H * 3 * sizeof(float)));
-    HIPCHK(hipMalloc((void**)&m->d_mean, (size_t)W * H * 3 * sizeof(float)));
-    HIPCHK(hipMalloc((void**)&m->d_u8, (size_t)W * H * 3));
+    HRTCHK(m->d_film.alloc((size_t)W * H * 3 * sizeof(float), "hipMalloc"));
+    HRTCHK(m->d_mean.alloc((size_t)W * H * 3 * sizeof(float), "hipMalloc"));
+    HRTCHK(m->d_u8.alloc((size_t)W * H * 3, "hipMalloc"));
     m->W = W; m->H = H; m->R = R;
     return HRT_OK;
 }
@@ -2913,42 +2889,39 @@ hrt_status hrt_multi_render(hrt_multi* m, const hrt_camera* cam, const hrt_param
                             const float* resume_sums, float* out_sums, uint8_t* out_u8, hrt_stats* stats) {
     HRT_API_TRY
     if (!m || !cam) return fail(HRT_ERR_INVALID, "NULL argument");
-    hrt_status st = check_params(pr);
-    if (st != HRT_OK) return st;
+    HRTCHK(check_params(pr));
     if (R <= 0) return fail(HRT_ERR_INVALID, "rows_per_block must be positive");
     if (sample_count < 0) sample_count = pr->samples - sample_first;
     if (sample_first < 0 || sample_count < 0 || sample_first + sample_count > pr->samples) return fail(HRT_ERR_INVALID, "sample range outside [0, samples)");
     const int G = (int)m->devices.size();
     const int W = pr->width, H = pr->height, W3 = W * 3;
-    st = multi_reserve(m, W, H, R);
-    if (st != HRT_OK) return st;
+    HRTCHK(multi_reserve(m, W, H, R));
     if (m->poisoned) {
         if (!resume_sums && !(sample_first == 0 && sample_count > 0))
             return fail(HRT_ERR_INVALID, "an earlier render of this session failed on one rank after others had added their samples: pass resume_sums or start again at sample 0");
         m->poisoned = false;
     }
     const long long n_film = (long long)H * W3;
-    auto blocks_for = [&](long long n) { return (int)std::min<long long>((n + 255) / 256, (long long)m->scenes[0]->n_cus * 8); };
+    auto blocks_for = [&](long long n) { return grid_for(m->scenes[0], n); };
 
     if (resume_sums) {   // a checkpoint's sums (film order) -> every rank's stripes
         HIPCHK(hipSetDevice(m->devices[0]));
-        HIPCHK(hipMemcpyAsync(m->d_film, resume_sums, (size_t)n_film * sizeof(float), hipMemcpyHostToDevice, m->streams[0]));
+        HIPCHK(hipMemcpyAsync(m->d_film.get(), resume_sums, (size_t)n_film * sizeof(float), hipMemcpyHostToDevice, m->streams[0]));
         HIPCHK(hipStreamSynchronize(m->streams[0]));
         for (int g = 0; g < G; ++g) {
             const int rows = hrt_stripe_rows(H, R, g, G);
             if (!rows) continue;
             HIPCHK(hipSetDevice(m->devices[g]));
-            float* src = m->d_film;
-            float* tmp = nullptr;
+            const float* src = m->d_film.get<float>();
+            DevBuf tmp;
             if (g != 0) {   // (rare path: through the host rather than a second collective)
-                HIPCHK(hipMalloc((void**)&tmp, (size_t)n_film * sizeof(float)));
-                HIPCHK(hipMemcpy(tmp, resume_sums, (size_t)n_film * sizeof(float), hipMemcpyHostToDevice));
-                src = tmp;
+                HRTCHK(tmp.alloc((size_t)n_film * sizeof(float), "hipMalloc"));
+                HIPCHK(hipMemcpy(tmp.get(), resume_sums, (size_t)n_film * sizeof(float), hipMemcpyHostToDevice));
+                src = tmp.get<float>();
             }
-            hipLaunchKernelGGL(k_restripe, dim3(blocks_for((long long)rows * W3)), dim3(256), 0, m->streams[g], src, m->d_accum[g], H, W3, R, G, g, rows);
+            hipLaunchKernelGGL(k_restripe, dim3(blocks_for((long long)rows * W3)), dim3(256), 0, m->streams[g], src, m->d_accum[g].get<float>(), H, W3, R, G, g, rows);
             HIPCHK(hipGetLastError());
             HIPCHK(hipStreamSynchronize(m->streams[g]));
-            if (tmp) (void)hipFree(tmp);
         }
     }
 
@@ -2958,7 +2931,7 @@ hrt_status hrt_multi_render(hrt_multi* m, const hrt_camera* cam, const hrt_param
     if (sample_count > 0) {
         auto work = [&](int g) {
             if (hrt_stripe_rows(H, R, g, G) == 0) return;      // more ranks than row blocks: nothing to do here
-            rst[g] = hrt_render_stripes_accumulate_device(m->scenes[g], cam, pr, R, g, G, m->d_accum[g], sample_first, sample_count, m->streams[g]);
+            rst[g] = hrt_render_stripes_accumulate_device(m->scenes[g], cam, pr, R, g, G, m->d_accum[g].get<float>(), sample_first, sample_count, m->streams[g]);
             if (rst[g] != HRT_OK) rerr[g] = g_err;
         };
         {
@@ -2982,7 +2955,7 @@ hrt_status hrt_multi_render(hrt_multi* m, const hrt_camera* cam, const hrt_param
         const RcclApi& rccl = rccl_api();
         NCCLCHK(rccl.GroupStart());
         for (int g = 0; g < G; ++g) {
-            ncclResult_t r = rccl.AllGather(m->d_accum[g], m->d_gather[g], (size_t)m->share, ncclFloat, m->comms[g], m->streams[g]);
+            ncclResult_t r = rccl.AllGather(m->d_accum[g].get(), m->d_gather[g].get(), (size_t)m->share, ncclFloat, m->comms[g], m->streams[g]);
             if (r != ncclSuccess) { (void)rccl.GroupEnd(); return fail_nccl(r, "ncclAllGather"); }
         }
         NCCLCHK(rccl.GroupEnd());
@@ -2991,7 +2964,7 @@ hrt_status hrt_multi_render(hrt_multi* m, const hrt_camera* cam, const hrt_param
         // (ordered behind its render, as the collective would be), and the first rank's stream waits for all of them
         for (int g = 0; g < G; ++g) {
             HIPCHK(hipSetDevice(m->devices[g]));
-            HIPCHK(hipMemcpyAsync(m->d_gather[0] + (size_t)g * m->share, m->d_accum[g], (size_t)m->share * sizeof(float), hipMemcpyDeviceToDevice, m->streams[g]));
+            HIPCHK(hipMemcpyAsync(m->gathered + (size_t)g * m->share, m->d_accum[g].get(), (size_t)m->share * sizeof(float), hipMemcpyDeviceToDevice, m->streams[g]));
             if (g == 0) continue;
             hipEvent_t ev;
             HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
@@ -3004,34 +2977,28 @@ hrt_status hrt_multi_render(hrt_multi* m, const hrt_camera* cam, const hrt_param
     // ---- first device: film order, preview mean, tonemap, copies
     HIPCHK(hipSetDevice(m->devices[0]));
     hipStream_t s0 = m->streams[0];
-    hipLaunchKernelGGL(k_unstripe, dim3(blocks_for(n_film)), dim3(256), 0, s0, m->d_gather[0], m->d_film, H, W3, R, G, m->share);
+    float* const film = m->d_film.get<float>();
+    hipLaunchKernelGGL(k_unstripe, dim3(blocks_for(n_film)), dim3(256), 0, s0, m->gathered, film, H, W3, R, G, m->share);
     HIPCHK(hipGetLastError());
-    if (out_sums) HIPCHK(hipMemcpyAsync(out_sums, m->d_film, (size_t)n_film * sizeof(float), hipMemcpyDeviceToHost, s0));
+    if (out_sums) HIPCHK(hipMemcpyAsync(out_sums, film, (size_t)n_film * sizeof(float), hipMemcpyDeviceToHost, s0));
     if (out_u8) {
         const int s_done = sample_first + sample_count;
-        const float* src = m->d_film;                                  // the last pass divided (main.cpp:126): the sums are the means
+        const float* src = film;                                       // the last pass divided (main.cpp:126): the sums are the means
         if (s_done < pr->samples) {
-            hipLaunchKernelGGL(k_preview_mean, dim3(blocks_for(n_film)), dim3(256), 0, s0, m->d_film, m->d_mean, n_film, static_cast<float>(s_done > 0 ? s_done : 1));
-            src = m->d_mean;
+            hipLaunchKernelGGL(k_preview_mean, dim3(blocks_for(n_film)), dim3(256), 0, s0, film, m->d_mean.get<float>(), n_film, static_cast<float>(s_done > 0 ? s_done : 1));
+            src = m->d_mean.get<float>();
         }
-        hipLaunchKernelGGL(k_resolve, dim3(blocks_for((long long)W * H)), dim3(256), 0, s0, src, (long long)W * H, m->d_u8);
+        hipLaunchKernelGGL(k_resolve, dim3(blocks_for((long long)W * H)), dim3(256), 0, s0, src, (long long)W * H, m->d_u8.get<uint8_t>());
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(out_u8, m->d_u8, (size_t)W * H * 3, hipMemcpyDeviceToHost, s0));
+        HIPCHK(hipMemcpyAsync(out_u8, m->d_u8.get(), (size_t)W * H * 3, hipMemcpyDeviceToHost, s0));
     }
     for (int g = G - 1; g >= 0; --g) { HIPCHK(hipSetDevice(m->devices[g])); HIPCHK(hipStreamSynchronize(m->streams[g])); }
     if (stats) {
         hrt_stats total{};
         for (int g = 0; g < G; ++g) {
             hrt_stats one;
-            st = hrt_scene_stats(m->scenes[g], &one);
-            if (st != HRT_OK) return st;
-            total.rays += one.rays; total.samples += one.samples; total.box_tests += one.box_tests; total.tri_tests += one.tri_tests;
-            total.mesh_hits += one.mesh_hits; total.env_lookups += one.env_lookups; total.launches += one.launches;
-            total.traversal_box_tests += one.traversal_box_tests; total.traversal_tri_tests += one.traversal_tri_tests;
-            total.shadow_rays += one.shadow_rays;
-            total.traversal_launches += one.traversal_launches;
-            if (one.kernel_ms > total.kernel_ms) total.kernel_ms = one.kernel_ms;          // the devices run side by side
-            if (one.traversal_ms > total.traversal_ms) total.traversal_ms = one.traversal_ms;
+            HRTCHK(hrt_scene_stats(m->scenes[g], &one));
+            add_stats(total, one);
         }
         *stats = total;
     }

@@ -84,6 +84,14 @@ bool readCheckpoint(const std::string& path, Checkpoint& ck, std::vector<float>&
     if (!ok) why = path + " is not a checkpoint of this film";
     return ok;
 }
+// Adds one pass's counters to a render's running total (the traversal_launches / traversal_ms pair is not summed).
+void addPassStats(hrt_stats& total, const hrt_stats& ps) {
+    total.rays += ps.rays; total.samples += ps.samples; total.box_tests += ps.box_tests; total.tri_tests += ps.tri_tests;
+    total.mesh_hits += ps.mesh_hits; total.env_lookups += ps.env_lookups; total.launches += ps.launches;
+    total.traversal_box_tests += ps.traversal_box_tests; total.traversal_tri_tests += ps.traversal_tri_tests;
+    total.shadow_rays += ps.shadow_rays;
+    total.kernel_ms += ps.kernel_ms;
+}
 // The adaptive render on the first device (hrt.h hrt_render_stripes_adaptive): passes until no pixel is active, the film is
 // sums / count.  Host buffers: one stripe partition (G = 1) is the film in row order.
 hrt_status renderAdaptive(const hrt_flat_scene& flat, const hrt_camera& cam, hrt_params pr, std::shared_ptr<Film>& film,
@@ -114,11 +122,7 @@ hrt_status renderAdaptive(const hrt_flat_scene& flat, const hrt_camera& cam, hrt
         hrt_stats ps{};
         st = hrt_render_stripes_adaptive(sc, &cam, &pr, opt.rows_per_block, 0, 1, &ad, sums.data(), sq.data(), count.data(), pass, &active, &ps);
         if (st != HRT_OK) break;
-        total.rays += ps.rays; total.samples += ps.samples; total.box_tests += ps.box_tests; total.tri_tests += ps.tri_tests;
-        total.mesh_hits += ps.mesh_hits; total.env_lookups += ps.env_lookups; total.launches += ps.launches;
-        total.traversal_box_tests += ps.traversal_box_tests; total.traversal_tri_tests += ps.traversal_tri_tests;
-        total.shadow_rays += ps.shadow_rays;
-        total.kernel_ms += ps.kernel_ms;
+        addPassStats(total, ps);
         if (active == 0) break;
         if (opt.progress) std::cout << "\rPass " << pass << ": " << active << "/" << numPixels << " pixels active" << std::flush;
         if (opt.on_pass) {   // preview: the mean of every pixel's samples so far
@@ -256,11 +260,7 @@ hrt_status render(int /*nThreads*/, const std::shared_ptr<Texture> background, c
             return st;
         }
         resolved = true;
-        total.rays += ps.rays; total.samples += ps.samples; total.box_tests += ps.box_tests; total.tri_tests += ps.tri_tests;
-        total.mesh_hits += ps.mesh_hits; total.env_lookups += ps.env_lookups; total.launches += ps.launches;
-        total.traversal_box_tests += ps.traversal_box_tests; total.traversal_tri_tests += ps.traversal_tri_tests;
-        total.shadow_rays += ps.shadow_rays;
-        total.kernel_ms += ps.kernel_ms;
+        addPassStats(total, ps);
         s_done += n;
         pathsBefore.store((long long)numPixels * (long long)s_done);
         if (!opt.checkpoint.empty()) {
