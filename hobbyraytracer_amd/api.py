@@ -32,7 +32,7 @@ TEX_SOLID, TEX_CHECKER, TEX_IMAGE, TEX_ENV = range(4)
 MAX_XFORMS = 4
 Q1_ROTQ_NORMALIZE, Q2_TRI_NO_TMIN, Q3_TRI_NO_FACE, Q4_SHEAR_FROM_ORIGIN = 1, 2, 4, 8
 QUIRKS_REFERENCE, QUIRKS_FIXED = 0xF, 0x0
-FLAG_STATS, FLAG_MEGAKERNEL, FLAG_TIMING, FLAG_THIN_LENS, FLAG_PROGRESS, FLAG_NEE = 1, 2, 4, 8, 16, 32
+FLAG_STATS, FLAG_MEGAKERNEL, FLAG_TIMING, FLAG_THIN_LENS, FLAG_PROGRESS, FLAG_NEE, FLAG_NEE_ENV = 1, 2, 4, 8, 16, 32, 64
 
 
 # ---------------------------------------------------------------- structs (hrt.h)
@@ -133,7 +133,7 @@ HIP_SYMBOLS = ["hrt_device_count", "hrt_scene_create", "hrt_scene_destroy", "hrt
                "hrt_resolve_u8_device", "hrt_closest_hit", "hrt_math_probe", "hrt_status_str", "hrt_last_error", "hrt_version",
                "hrt_multi_create", "hrt_multi_destroy", "hrt_multi_devices", "hrt_multi_uses_rccl", "hrt_multi_render", "hrt_bvh_build_device", "hrt_bvh_build_sah",
                "hrt_debug_bounds_violations", "hrt_scene_progress", "hrt_multi_progress",
-               "hrt_render_stripes_adaptive_device", "hrt_render_stripes_adaptive", "hrt_adaptive_mean_device"]
+               "hrt_render_stripes_adaptive_device", "hrt_render_stripes_adaptive", "hrt_adaptive_mean_device", "hrt_env_table_build"]
 HOST_SYMBOLS = ["hrt_host_load_yaml", "hrt_host_free", "hrt_host_flat", "hrt_host_film", "hrt_host_camera", "hrt_host_bvh_depth",
                 "hrt_default_params", "hrt_asset_write_teapot_obj", "hrt_asset_write_bust_obj", "hrt_asset_write_hall_hdr",
                 "hrt_host_write_image", "hrt_host_read_hdr", "hrt_host_read_png", "hrt_host_read_jpeg", "hrt_host_write_hdr", "hrt_host_write_pfm", "hrt_host_read_pfm", "hrt_host_last_error", "hrt_host_set_bvh_builder"]
@@ -190,6 +190,7 @@ _hip.hrt_multi_uses_rccl.argtypes = [_vp]
 _hip.hrt_multi_uses_rccl.restype = C.c_int32
 _hip.hrt_multi_render.argtypes = [_vp, C.POINTER(Camera), C.POINTER(Params), C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _u8p, C.POINTER(Stats)]
 _hip.hrt_math_probe.argtypes = [C.c_int, C.c_int32, C.c_int64, _fp, _fp, _fp]
+_hip.hrt_env_table_build.argtypes = [_fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp]
 
 _host.hrt_host_last_error.restype = C.c_char_p
 _host.hrt_host_load_yaml.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(_vp)]
@@ -237,8 +238,9 @@ def _ptr(a, t=_fp):
 
 # ---------------------------------------------------------------- host side
 def default_params(width, height, samples, quirks=QUIRKS_REFERENCE, seed=0, max_depth=50, stats=False, megakernel=False, timing=False,
-                   thin_lens=False, progress=False, nee=False):
-    """nee: next-event estimation with MIS for the scene's rect and sphere lights (FLAG_NEE)."""
+                   thin_lens=False, progress=False, nee=False, nee_env=False):
+    """nee: next-event estimation with MIS for the scene's rect and sphere lights (FLAG_NEE).
+    nee_env: also importance-sample the environment map (FLAG_NEE_ENV); implies nee."""
     p = Params()
     _host.hrt_default_params(C.byref(p), width, height, samples)
     p.quirks = quirks
@@ -246,7 +248,7 @@ def default_params(width, height, samples, quirks=QUIRKS_REFERENCE, seed=0, max_
     p.seed_hi = (seed >> 32) & 0xFFFFFFFF
     p.max_depth = max_depth
     p.flags = (FLAG_STATS if stats else 0) | (FLAG_MEGAKERNEL if megakernel else 0) | (FLAG_TIMING if timing else 0) | \
-              (FLAG_THIN_LENS if thin_lens else 0) | (FLAG_PROGRESS if progress else 0) | (FLAG_NEE if nee else 0)
+              (FLAG_THIN_LENS if thin_lens else 0) | (FLAG_PROGRESS if progress else 0) | (FLAG_NEE if nee or nee_env else 0) | (FLAG_NEE_ENV if nee_env else 0)
     return p
 
 
@@ -394,6 +396,20 @@ def bvh_build_device(tri_pos, max_leaf=2, device=0, algo="lbvh"):
     f.restype = C.c_int
     _check(f(device, pos.ctypes.data, n, max_leaf, nodes.ctypes.data, C.addressof(n_nodes), order.ctypes.data, C.addressof(depth)))
     return nodes[:n_nodes.value], order, depth.value
+
+
+def env_table_build(texels):
+    """FLAG_NEE_ENV's sampling table of an environment map (hrt_env_table_build), built on the current device by the
+    kernels hrt_scene_create runs.  texels: [H, W, C >= 3] fp32, rows from the top.  Returns (marginal [H + 1], conditional [H, W + 1])
+    fp32 CDFs, or None when the map has no table (total weight 0 or not finite)."""
+    t = np.ascontiguousarray(texels, np.float32)
+    if t.ndim != 3 or t.shape[2] < 3:
+        raise ValueError("texels must be [H, W, C >= 3]")
+    H, W, ch = t.shape
+    marg = np.zeros(H + 1, np.float32)
+    cond = np.zeros((H, W + 1), np.float32)
+    _check(_hip.hrt_env_table_build(_ptr(t), W, H, ch, _ptr(marg), _ptr(cond)))
+    return None if marg[H] == 0.0 else (marg, cond)
 
 
 def stripe_rows(height, rows_per_block, rank, n_ranks):

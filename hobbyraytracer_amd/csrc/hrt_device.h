@@ -1388,6 +1388,119 @@ __device__ inline vec3 background_value(const DScene& sc, vec3 d) {
     return tex_value(sc, sc.background_tex, u, v, vec3(0.0f));
 }
 
+// ------------------------------------------------------------------ environment-map importance sampling (HRT_FLAG_NEE_ENV)
+// The map as a light: texel (i, j) of a W x H HRT_TEX_ENV background is what background_value returns for every direction whose
+// u = atan2(z, x) / 2 pi + 0.5, v = acos(y) / pi land on i = int(u (W - 1) + 0.5), j = int(v (H - 1) + 0.5), i.e. u in
+// [max(0, (i - 1/2) / (W - 1)), min(1, (i + 1/2) / (W - 1))] (the first and last columns and rows are half cells; W = 1 or H = 1:
+// one cell spans the whole range).  As angles: phi = 2 pi (u - 1/2), theta = pi v, direction (sin theta cos phi, cos theta,
+// sin theta sin phi), solid angle dphi (cos theta_lo - cos theta_hi).
+// The table (built on the device by hrt_hip.hip k_env_rows / k_env_marginal): marg = H + 1 floats, the CDF over rows; cond = H rows of
+// W + 1 floats, the CDF over a row's columns; weights lum(texel) x solid angle; first entries 0, last 1, monotone.
+#define HRT_ENV_PI 3.14159265358979323846264338327950288
+
+__device__ inline float env_sin(float x) { return gsin(x); }
+__device__ inline float env_cos(float x) { return gcos(x); }
+__device__ inline double env_sin(double x) { return sin(x); }
+__device__ inline double env_cos(double x) { return cos(x); }
+// the range [lo, lo + len] of texel k of n along one axis of the lookup, as a fraction of the axis' range (len directly: hi - lo
+// would cancel in fp32 at the last texel)
+template <class T>
+__device__ inline void env_edges(int k, int n, T& lo, T& len) {
+    if (n <= 1) { lo = T(0); len = T(1); return; }
+    lo = k == 0 ? T(0) : (T(k) - T(0.5)) / T(n - 1);
+    len = (k == 0 || k == n - 1 ? T(0.5) : T(1)) / T(n - 1);
+}
+// Cell (i, j): phi in [phi0, phi0 + dphi], cos theta in [c0 - dc, c0] (c0 = cos theta_lo); its solid angle is dphi x dc.
+// dc = cos theta_lo - cos theta_hi = 2 sin(dtheta / 2) sin(mean theta), without the cancellation near the poles.
+template <class T>
+__device__ inline void env_cell_bounds(int i, int j, int W, int H, T& phi0, T& dphi, T& c0, T& dc) {
+    T u0, du, v0, dv;
+    env_edges<T>(i, W, u0, du);
+    // a row of the lower half from its mirror image (theta -> pi - theta): pi v near pi would carry the rounding of pi itself
+    const bool low = j > H - 1 - j;
+    env_edges<T>(low ? H - 1 - j : j, H, v0, dv);
+    const T pi = T(HRT_ENV_PI);
+    phi0 = T(2) * pi * (u0 - T(0.5));
+    dphi = T(2) * pi * du;
+    const T th0 = pi * v0;
+    const T cm = env_cos(th0);
+    dc = T(2) * env_sin(T(0.5) * (pi * dv)) * env_sin(th0 + T(0.5) * (pi * dv));
+    c0 = low ? dc - cm : cm;          // mirror: cos theta_lo = -(cos of the mirror row's theta_hi)
+}
+template <class T>
+__device__ inline T env_cell_solid_angle(int i, int j, int W, int H) {
+    T phi0, dphi, c0, dc;
+    env_cell_bounds<T>(i, j, W, H, phi0, dphi, c0, dc);
+    return dphi * dc;
+}
+// The texel background_value reads for direction d: the same operations as background_value and tex_leaf's HRT_TEX_ENV branch.
+__device__ inline void env_cell_of(vec3 d, int W, int H, int& i, int& j) {
+    const float pi = 3.14159265358979323846264338327950288f;
+    vec3 nD = normalize(d);
+    float phi = gatan2(nD.z, nD.x);
+    float theta = gacos(nD.y);
+    float u = phi / (2 * pi) + 0.5f;
+    float v = theta / pi;
+    u = gclamp(u, 0.0f, 1.0f);
+    v = gclamp(v, 0.0f, 1.0f);
+    i = texel_index((u * (W - 1)) + 0.5f);
+    j = texel_index((v * (H - 1)) + 0.5f);
+    if (i > W - 1) i = W - 1;     // (never, for u <= 1: the table is read with these indices)
+    if (j > H - 1) j = H - 1;
+}
+// The first of n intervals of the CDF whose upper bound exceeds x (cdf[n] = 1 > x): intervals of zero width are never chosen.
+__device__ inline int env_search(const float* cdf, int n, float x) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (cdf[mid + 1] > x) hi = mid;
+        else lo = mid + 1;
+    }
+    return lo;
+}
+// P(cell) = P_row(j) P_col(i | j), both differences of the stored fp32 CDFs (so that sampler and density agree)
+__device__ inline float env_cell_prob(const float* marg, const float* cond, int W, int i, int j) {
+    const float* row = cond + (size_t)j * (size_t)(W + 1);
+    return (marg[j + 1] - marg[j]) * (row[i + 1] - row[i]);
+}
+// One RNG_ENV draw u -> a direction w of the table's distribution: x picks the row, y the column, z phi uniform in the cell, w cos theta
+// uniform in the cell.  pdf = P(cell) / solid angle, (ci, cj) = the cell.  false: the cell has no probability (an invalid table).
+__device__ inline bool env_sample(const float* marg, const float* cond, int W, int H, u32x4 u, vec3& w, float& pdf, int& ci, int& cj) {
+    const int j = env_search(marg, H, u01(u.x));
+    const int i = env_search(cond + (size_t)j * (size_t)(W + 1), W, u01(u.y));
+    const float p = env_cell_prob(marg, cond, W, i, j);
+    float phi0, dphi, c0, dc;
+    env_cell_bounds<float>(i, j, W, H, phi0, dphi, c0, dc);
+    const float ct = gclamp(c0 - u01(u.w) * dc, -1.0f, 1.0f);
+    const float st = sqrtf((1.0f - ct) * (1.0f + ct));
+    float sp, cp;
+    gsincos(phi0 + u01(u.z) * dphi, sp, cp);
+    w = vec3(st * cp, ct, st * sp);
+    const float omega = dphi * dc;
+    pdf = p / omega;
+    ci = i; cj = j;
+    return p > 0.0f && omega > 0.0f;
+}
+// p_env of direction d (any length): the density env_sample gives the cell background_value reads for d; 0 on a texel of weight 0.
+__device__ inline float env_pdf(const float* marg, const float* cond, int W, int H, vec3 d) {
+    int i, j;
+    env_cell_of(d, W, H, i, j);
+    const float p = env_cell_prob(marg, cond, W, i, j);
+    if (!(p > 0.0f)) return 0.0f;
+    return p / env_cell_solid_angle<float>(i, j, W, H);
+}
+// The table's weight of one texel (float64): lum x solid angle; 0 for a negative, NaN or infinite channel.  row_dc = the row's dc.
+__device__ inline double env_texel_weight(const float* px, int i, int W, double row_dc) {
+    const float r = px[0], g = px[1], b = px[2];
+    const float big = 3.402823466e38f;
+    if (!(r >= 0.0f && r <= big && g >= 0.0f && g <= big && b >= 0.0f && b <= big)) return 0.0;
+    double u0, du;
+    env_edges<double>(i, W, u0, du);
+    const double dphi = 2.0 * HRT_ENV_PI * du;
+    const double lum = 0.2126 * (double)r + 0.7152 * (double)g + 0.0722 * (double)b;
+    return lum * (dphi * row_dc);
+}
+
 // ------------------------------------------------------------------ render() / rayColour() pieces (main.cpp)
 struct PathState {
     vec3 o, d;          // current ray

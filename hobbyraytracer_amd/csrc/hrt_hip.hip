@@ -13,7 +13,8 @@
 //   k_closest_hit       world->hit() for test rays (parity tests).
 //   k_math_probe        the shared math kernels, for CPU==GPU bit tests.
 //   k_ad_select / k_ad_scan / k_wf_reduce_list / k_ad_mean   adaptive sampling.
-//   k_wf_shade<STATS, true> / k_wf_shadow   next-event estimation with MIS, HRT_FLAG_NEE.
+//   k_wf_shade<STATS, true> / k_wf_shadow<false>   next-event estimation with MIS, HRT_FLAG_NEE.
+//   k_wf_shade<STATS, true, true> / k_wf_shadow<true> / k_env_rows / k_env_marginal   environment-map sampling, HRT_FLAG_NEE_ENV (4.6).
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>   // types and prototypes only: the library is loaded on demand (rccl_api below)
 #include <dlfcn.h>
@@ -332,6 +333,10 @@ struct WfBuf {
     const float4* lights;        // the light table (hrt_device.h HRT_NEE_REC float4 per light)
     const int32_t* light_of;     // per prim: its index in the table, -1 if it is not a table light
     int n_lights;
+    // HRT_FLAG_NEE_ENV only: the environment map's sampling table (hrt_device.h env_*), W x H texels
+    const float* env_marg;
+    const float* env_cond;
+    int env_w, env_h;
 };
 // Task ownership.  Tasks differ in cost by orders of magnitude (a run of pixels under the mesh vs. a run of sky), so a
 // static wave -> task map leaves most waves idle while a few finish: plain striding (task = wave + i * n_waves) even
@@ -1011,12 +1016,13 @@ __global__ __launch_bounds__(HRT_BLOCK) __attribute__((amdgpu_waves_per_eu(DEPTH
 // together: the environment lookup (normalize, atan2, acos, texel fetch: ~300 instructions) otherwise runs at
 // the 10 % lane occupancy of "the lanes of this chunk that happened to miss".
 #define HRT_MISSQ_CAP 128
-struct MissQueue {            // one per wave; SoA rows of HRT_MISSQ_CAP entries: d.xyz, atten.xyz, slot
-    float* f;                 // 6 rows
+struct MissQueue {            // one per wave; SoA rows of HRT_MISSQ_CAP entries: d.xyz, atten.xyz, [prev_pb,] slot
+    float* f;                 // 6 rows (HRT_FLAG_NEE_ENV: 7, the last one the previous vertex's p_b, -1: not eligible)
     unsigned* slot;           // 1 row
     unsigned count;           // wave-uniform
 };
-template <bool STATS>
+// HRT_FLAG_NEE_ENV (ENV): the background of an escape from an eligible vertex is weighted by nee_mis_bsdf(prev_pb, p_env)
+template <bool STATS, bool ENV = false>
 __device__ inline void missq_flush(const DScene& sc, const WfBuf& w, MissQueue& q, unsigned lane, unsigned n, PathCounters& pc) {
     // the last n (<= 64) entries
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -1027,7 +1033,14 @@ __device__ inline void missq_flush(const DScene& sc, const WfBuf& w, MissQueue& 
         const unsigned slot = q.slot[e];
         if (STATS && sc.ltexs[sc.background_tex].kind == HRT_TEX_ENV) pc.env_lookups++;
         vec3 result(0.0f);
-        result += atten * background_value(sc, d);       // path_shade's miss branch, same operations
+        if (ENV) {
+            vec3 bg = background_value(sc, d);
+            const float prev_pb = q.f[6 * HRT_MISSQ_CAP + e];
+            if (prev_pb >= 0.0f) bg = bg * nee_mis_bsdf(prev_pb, env_pdf(w.env_marg, w.env_cond, w.env_w, w.env_h, d));
+            result += atten * bg;
+        } else {
+            result += atten * background_value(sc, d);   // path_shade's miss branch, same operations
+        }
         w.rad[slot] = make_float4(result.x, result.y, result.z, 0.0f);
     }
     q.count -= n;
@@ -1071,7 +1084,7 @@ __device__ HRT_WAVE_FN bool path_shade_nee(const DScene& sc, const hrt_params& p
     return ps.bounce >= pr.max_depth;
 }
 
-template <bool STATS, bool NEE = false>
+template <bool STATS, bool NEE = false, bool ENV = false>
 __device__ HRT_WAVE_FN void wf_shade_task(const DScene& sc, const hrt_params& pr, const RenderMap& map, const WfScene& ws, unsigned n_local, int s0, int round,
                                      const WfBuf& w, unsigned task, unsigned n, unsigned lane, unsigned long long lt, MissQueue& mq,
                                      PathCounters& pc, unsigned& n_seg, unsigned& n_culled, unsigned& live_out, unsigned& qn_out, unsigned& rn_out) {
@@ -1090,6 +1103,8 @@ __device__ HRT_WAVE_FN void wf_shade_task(const DScene& sc, const hrt_params& pr
         rng_ctx ctx; ctx.seed_lo = 0; ctx.seed_hi = 0; ctx.pixel = 0; ctx.sample = 0; ctx.bounce = 0;
         bool missed = false;
         WorldHit wh; wh.prim = -1; wh.sub = -1; wh.t = 0.0f; wh.s_prim = -1; wh.s_sub = -1; wh.s_t = 0.0f;
+        float prev_pb = -1.0f;       // ENV: the previous vertex's p_b (the miss queue needs it too)
+        if (ENV && round > 0 && j0 + lane < n) prev_pb = w.N[par][pos].w;
         if (j0 + lane < n) {
             n_seg++;
             ps.o = vec3(a.x, a.y, a.z); ps.d = vec3(a.w, b.x, b.y);
@@ -1110,17 +1125,19 @@ __device__ HRT_WAVE_FN void wf_shade_task(const DScene& sc, const hrt_params& pr
                     const unsigned e = mq.count + lanes_below(mm);
                     mq.f[0 * HRT_MISSQ_CAP + e] = ps.d.x; mq.f[1 * HRT_MISSQ_CAP + e] = ps.d.y; mq.f[2 * HRT_MISSQ_CAP + e] = ps.d.z;
                     mq.f[3 * HRT_MISSQ_CAP + e] = ps.atten.x; mq.f[4 * HRT_MISSQ_CAP + e] = ps.atten.y; mq.f[5 * HRT_MISSQ_CAP + e] = ps.atten.z;
+                    if (ENV) mq.f[6 * HRT_MISSQ_CAP + e] = prev_pb;
                     mq.slot[e] = slot;
                 }
                 mq.count += (unsigned)__popcll(mm);       // <= 63 + 64 < HRT_MISSQ_CAP
-                if (mq.count >= 64) missq_flush<STATS>(sc, w, mq, lane, 64, pc);
+                if (mq.count >= 64) missq_flush<STATS, ENV>(sc, w, mq, lane, 64, pc);
             }
         }
         HRT_SP_MARK(1);
         float4 nrec = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
         if (j0 + lane < n && !missed) {
             bool ended;
-            if (NEE) ended = path_shade_nee<STATS>(sc, pr, w, ctx, ps, wh, pc, round > 0 ? w.N[par][pos].w : -1.0f, nrec);
+            if (ENV) ended = path_shade_nee<STATS>(sc, pr, w, ctx, ps, wh, pc, prev_pb, nrec);
+            else if (NEE) ended = path_shade_nee<STATS>(sc, pr, w, ctx, ps, wh, pc, round > 0 ? w.N[par][pos].w : -1.0f, nrec);
             else ended = path_shade<STATS>(sc, pr, ctx, ps, wh, pc);
             if (ended) w.rad[slot] = make_float4(ps.result.x, ps.result.y, ps.result.z, 0.0f);
             else {
@@ -1173,28 +1190,29 @@ __device__ HRT_WAVE_FN void wf_shade_counters(const WfBuf& w, DeviceCounters* co
 #ifndef HRT_SHADE_WAVES
 #define HRT_SHADE_WAVES 4   // waves per SIMD the register allocator must leave room for (<= 128 VGPRs)
 #endif
-template <bool STATS, bool NEE>
+// ENV (HRT_FLAG_NEE_ENV, with NEE only): the environment map's MIS weight on escapes from eligible vertices
+template <bool STATS, bool NEE, bool ENV = false>
 __global__ __launch_bounds__(256, HRT_SHADE_WAVES) void k_wf_shade(DScene sc, hrt_params pr, RenderMap map, WfScene ws, unsigned n_local, int s0, int round,
                                                   WfBuf w, DeviceCounters* counters) {
     const unsigned lane = threadIdx.x & 63u;
     const unsigned wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const unsigned long long lt = (1ull << lane) - 1ull;
     __shared__ __attribute__((aligned(16))) uint32_t s_tables[HRT_TABLE_LDS_BYTES / 4];
-    __shared__ float s_missq[4][7 * HRT_MISSQ_CAP];
+    __shared__ float s_missq[4][(ENV ? 8 : 7) * HRT_MISSQ_CAP];
 #ifdef HRT_SHADE_PROFILE
     g_prof_counters = counters;
 #endif
     stage_tables(sc, s_tables);
     MissQueue mq;
-    mq.f = s_missq[threadIdx.x >> 6]; mq.slot = (unsigned*)(mq.f + 6 * HRT_MISSQ_CAP); mq.count = 0;
+    mq.f = s_missq[threadIdx.x >> 6]; mq.slot = (unsigned*)(mq.f + (ENV ? 7 : 6) * HRT_MISSQ_CAP); mq.count = 0;
     unsigned n_seg = 0, n_culled = 0;
     PathCounters pc; pc.rays = 0; pc.samples = 0; pc.mesh_hits = 0; pc.env_lookups = 0; pc.bvh.box_tests = 0; pc.bvh.tri_tests = 0;
     HRT_FOR_MY_TASKS(task, w, wave, lane) {
         unsigned live, qn, rn;
-        wf_shade_task<STATS, NEE>(sc, pr, map, ws, n_local, s0, round, w, task, HRT_UNIFORM(w.live[task]), lane, lt, mq, pc, n_seg, n_culled, live, qn, rn);
+        wf_shade_task<STATS, NEE, ENV>(sc, pr, map, ws, n_local, s0, round, w, task, HRT_UNIFORM(w.live[task]), lane, lt, mq, pc, n_seg, n_culled, live, qn, rn);
         if (lane == 0) { w.live[task] = live; w.qn[task] = qn; w.rn[task] = rn; if (rn) wf_ref_publish(w, task, rn); }
     }
-    if (mq.count) missq_flush<STATS>(sc, w, mq, lane, mq.count, pc);
+    if (mq.count) missq_flush<STATS, ENV>(sc, w, mq, lane, mq.count, pc);
     wf_shade_counters<STATS>(w, counters, wave, lane, n_seg, n_culled, pc);
 }
 
@@ -1207,7 +1225,12 @@ __global__ __launch_bounds__(256, HRT_SHADE_WAVES) void k_wf_shade(DScene sc, hr
 // world_hit of 64 shadow rays runs with full lanes whatever fraction of the survivors is eligible (metal, glass and media are not).
 // -DHRT_NEE_UNIT_SHADOW (experiment only): cast the shadow ray with the unit direction w instead of t_k w -- the biased
 // estimator the design avoids, kept compilable so the unbiasedness test can be shown to catch it.
+// ENV (HRT_FLAG_NEE_ENV): after the table-light sample (if the scene has table lights), the same vertex takes one
+// environment sample: a direction from one RNG_ENV draw (env_sample), the ray d = t_k w with t_max = inf that sees the sky when
+// world_hit misses (media: bounce field round | HRT_RNG_SHADOW | HRT_RNG_SHADOW_ENV), and the term atten background pb p_env /
+// (pb^2 + p_env^2), added to `direct` after the table-light term.
 #define HRT_SHADOWQ_CAP 128
+template <bool ENV>
 __global__ __launch_bounds__(HRT_BLOCK) void k_wf_shadow(DScene sc, hrt_params pr, RenderMap map, unsigned n_local, int s0, int round, WfBuf w) {
     __shared__ int s_stack[HRT_STACK_DEPTH * HRT_BLOCK];
     __shared__ __attribute__((aligned(16))) uint32_t s_tables[HRT_TABLE_LDS_BYTES / 4];
@@ -1251,36 +1274,109 @@ __global__ __launch_bounds__(HRT_BLOCK) void k_wf_shadow(DScene sc, hrt_params p
         const float4 a = w.S0[nxt][pos], b = w.S1[nxt][pos];
         const float az = w.S3[nxt][pos];
         const unsigned slot = __float_as_uint(w.S2[nxt][pos].w);
-        rng_ctx ctx = slot_ctx(pr, map, slot, n_local, s0, round);
-        const u32x4 u = rng_draw(ctx, RNG_LIGHT, 0);
-        const int li = nee_choose(w.lights, w.n_lights, u.x);
-        const float4 L0 = w.lights[HRT_NEE_REC * li], L1 = w.lights[HRT_NEE_REC * li + 1], L2 = w.lights[HRT_NEE_REC * li + 2];
         const vec3 x(a.x, a.y, a.z);
-        vec3 wd;
-        float pl, reach;
-        if (!nee_sample(L0, L1, L2, x, u.y, u.z, wd, pl, reach)) continue;
-        float t0, t1;
-        const float pb = nee_bsdf_pdf(vec3(nr.x, nr.y, nr.z), wd, t0, t1);
-        if (!(pb > 0.0f)) continue;
+        [&]() {   // the table-light sample (a lambda: `return` ends it, and the environment sample below still runs)
+            if (ENV && w.n_lights == 0) return;
+            rng_ctx ctx = slot_ctx(pr, map, slot, n_local, s0, round);
+            const u32x4 u = rng_draw(ctx, RNG_LIGHT, 0);
+            const int li = nee_choose(w.lights, w.n_lights, u.x);
+            const float4 L0 = w.lights[HRT_NEE_REC * li], L1 = w.lights[HRT_NEE_REC * li + 1], L2 = w.lights[HRT_NEE_REC * li + 2];
+            vec3 wd;
+            float pl, reach;
+            if (!nee_sample(L0, L1, L2, x, u.y, u.z, wd, pl, reach)) return;
+            float t0, t1;
+            const float pb = nee_bsdf_pdf(vec3(nr.x, nr.y, nr.z), wd, t0, t1);
+            if (!(pb > 0.0f)) return;
 #ifdef HRT_NEE_UNIT_SHADOW
-        const float tk = 1.0f;
+            const float tk = 1.0f;
 #else
-        const float tk = nee_pick_root(t0, t1, u.w);
+            const float tk = nee_pick_root(t0, t1, u.w);
 #endif
-        const vec3 d = tk * wd;
-        ctx.bounce = (uint32_t)round | HRT_RNG_SHADOW;
-        ++n_shadow;
-        DCounters cnt; cnt.box_tests = 0; cnt.tri_tests = 0;
-        const WorldHit wh = world_hit<false>(sc, x, d, pr.t_min, reach / tk * 1.001f, pr.quirks, ctx, stack, cnt);
-        if (wh.prim != __float_as_int(L0.x)) continue;
-        DRec rec;
-        hit_record(sc, wh, x, d, pr.quirks, pr.t_min, rec);
-        const vec3 term = vec3(b.z, b.w, az) * nee_emitted(sc, rec) * nee_mis_shadow(pb, L0.z * pl);
-        const float4 acc = w.direct[slot];
-        w.direct[slot] = make_float4(acc.x + term.x, acc.y + term.y, acc.z + term.z, 0.0f);
+            const vec3 d = tk * wd;
+            ctx.bounce = (uint32_t)round | HRT_RNG_SHADOW;
+            ++n_shadow;
+            DCounters cnt; cnt.box_tests = 0; cnt.tri_tests = 0;
+            const WorldHit wh = world_hit<false>(sc, x, d, pr.t_min, reach / tk * 1.001f, pr.quirks, ctx, stack, cnt);
+            if (wh.prim != __float_as_int(L0.x)) return;
+            DRec rec;
+            hit_record(sc, wh, x, d, pr.quirks, pr.t_min, rec);
+            const vec3 term = vec3(b.z, b.w, az) * nee_emitted(sc, rec) * nee_mis_shadow(pb, L0.z * pl);
+            const float4 acc = w.direct[slot];
+            w.direct[slot] = make_float4(acc.x + term.x, acc.y + term.y, acc.z + term.z, 0.0f);
+        }();
+        if (ENV) {   // the environment sample of the same vertex
+            rng_ctx ctx = slot_ctx(pr, map, slot, n_local, s0, round);
+            vec3 we;
+            float pe, t0, t1;
+            int ci, cj;
+            if (!env_sample(w.env_marg, w.env_cond, w.env_w, w.env_h, rng_draw(ctx, RNG_ENV, 0), we, pe, ci, cj)) continue;
+            const float pb = nee_bsdf_pdf(vec3(nr.x, nr.y, nr.z), we, t0, t1);
+            if (!(pb > 0.0f)) continue;
+            const vec3 d = nee_pick_root(t0, t1, rng_draw(ctx, RNG_ENV, 1).x) * we;
+            pe = env_pdf(w.env_marg, w.env_cond, w.env_w, w.env_h, d);   // the density of the texel background_value reads for d
+            if (!(pe > 0.0f)) continue;
+            ctx.bounce = (uint32_t)round | HRT_RNG_SHADOW | HRT_RNG_SHADOW_ENV;
+            ++n_shadow;
+            DCounters cnt; cnt.box_tests = 0; cnt.tri_tests = 0;
+            const WorldHit wh = world_hit<false>(sc, x, d, pr.t_min, __builtin_huge_valf(), pr.quirks, ctx, stack, cnt);
+            if (wh.prim >= 0) continue;
+            const vec3 term = vec3(b.z, b.w, az) * background_value(sc, d) * nee_mis_shadow(pb, pe);
+            const float4 acc = w.direct[slot];
+            w.direct[slot] = make_float4(acc.x + term.x, acc.y + term.y, acc.z + term.z, 0.0f);
+        }
     }
     const unsigned c = wave_sum(n_shadow);
     if (lane == 0 && c) w.wave_shadow[wave] += (unsigned long long)c;      // this wave's own cell
+}
+
+// HRT_FLAG_NEE_ENV's sampling table (hrt_device.h env_*).  One CDF of n float64 weights per block of 256 threads, in a fixed
+// order and without atomics, so that every device builds the same bits: thread t sums the contiguous run [t c, (t + 1) c) of the weights
+// (c = ceil(n / 256)); thread 0 scans the 256 run totals in order; thread t then writes excl[t] + (its run's prefix) / total.  The
+// last run ends on excl[256] = total itself, and x + a <= x + b for a <= b: the values are monotone and the last one is exactly 1.
+// A total of 0 (or not finite) writes 0 everywhere but out[n] = 1.  Returns the total (every thread).
+template <class Weight>
+__device__ inline double env_block_cdf(int n, Weight weight, float* __restrict__ out, double* s_run) {
+    const int t = threadIdx.x;
+    const int c = (n + 255) / 256;
+    const int i0 = min(n, t * c), i1 = min(n, i0 + c);
+    double own = 0.0;
+    for (int i = i0; i < i1; ++i) own += weight(i);
+    s_run[t] = own;
+    __syncthreads();
+    if (t == 0) {
+        double run = 0.0;
+        for (int k = 0; k < 256; ++k) { const double v = s_run[k]; s_run[k] = run; run += v; }
+        s_run[256] = run;
+    }
+    __syncthreads();
+    const double total = s_run[256];
+    const bool ok = total > 0.0 && total <= 1.7976931348623157e308;
+    double local = 0.0;
+    for (int i = i0; i < i1; ++i) {
+        local += weight(i);
+        out[i + 1] = ok ? (float)((s_run[t] + local) / total) : 0.0f;
+    }
+    __syncthreads();
+    if (t == 0) { out[0] = 0.0f; out[n] = 1.0f; }
+    return total;
+}
+// one block per row j: the row's conditional CDF (W + 1 floats) and its total weight
+__global__ __launch_bounds__(256) void k_env_rows(const float* __restrict__ texels, int W, int H, int channels, float* __restrict__ cond,
+                                                  double* __restrict__ row_total) {
+    __shared__ double s_run[257];
+    const int j = blockIdx.x;
+    double phi0, dphi, c0, dc;
+    env_cell_bounds<double>(0, j, W, H, phi0, dphi, c0, dc);
+    const float* row = texels + (size_t)j * (size_t)W * (size_t)channels;
+    const double total = env_block_cdf(W, [&](int i) { return env_texel_weight(row + (size_t)i * (size_t)channels, i, W, dc); },
+                                       cond + (size_t)j * (size_t)(W + 1), s_run);
+    if (threadIdx.x == 0) row_total[j] = total;
+}
+// one block: the marginal CDF over the rows (H + 1 floats); total[0] = the map's total weight
+__global__ __launch_bounds__(256) void k_env_marginal(const double* __restrict__ row_total, int H, float* __restrict__ marg, double* __restrict__ total) {
+    __shared__ double s_run[257];
+    const double t = env_block_cdf(H, [&](int j) { return row_total[j]; }, marg, s_run);
+    if (threadIdx.x == 0) total[0] = t;
 }
 
 // Every remaining round [round0, rounds_end) of a task in one go, by the wave that pulled the task.  Rounds are a
@@ -1663,6 +1759,9 @@ struct hrt_scene {
     float4* d_lights = nullptr;
     int32_t* d_light_of = nullptr;
     int n_lights = 0;
+    // HRT_FLAG_NEE_ENV: the environment background's sampling table, built at hrt_scene_create; empty: no table
+    DevBuf env_marg, env_cond;
+    int env_w = 0, env_h = 0;
 };
 
 namespace {
@@ -1869,7 +1968,23 @@ hrt_status check_params(const hrt_params* p) {
     // the wavefront pipeline enqueues two launches and 3 KB of counters per round whether paths are left or not
     if (p->max_depth > 65536) return fail(HRT_ERR_UNSUPPORTED, "max_depth above 65536 (the reference's is 50, main.cpp:32)");
     if (!(p->t_min == p->t_min)) return fail(HRT_ERR_INVALID, "t_min is NaN");
+    if ((p->flags & HRT_FLAG_NEE_ENV) && !(p->flags & HRT_FLAG_NEE)) return fail(HRT_ERR_INVALID, "HRT_FLAG_NEE_ENV needs HRT_FLAG_NEE");
     if ((p->flags & HRT_FLAG_MEGAKERNEL) && (p->flags & HRT_FLAG_NEE)) return fail(HRT_ERR_UNSUPPORTED, "next-event estimation renders on the wavefront pipeline only");
+    return HRT_OK;
+}
+
+// HRT_FLAG_NEE_ENV's table of the W x H x channels fp32 texels at d_texels (device memory) into d_marg (H + 1 floats) and d_cond
+// (H x (W + 1)); *has = whether the map has a table (total weight > 0 and finite).  Synchronous.
+hrt_status env_table_device(const float* d_texels, int W, int H, int channels, float* d_marg, float* d_cond, bool* has) {
+    DevBuf d_rows, d_total;
+    HRTCHK(d_rows.alloc((size_t)H * sizeof(double), "hipMalloc(env table)"));
+    HRTCHK(d_total.alloc(sizeof(double), "hipMalloc(env table)"));
+    hipLaunchKernelGGL(k_env_rows, dim3((unsigned)H), dim3(256), 0, 0, d_texels, W, H, channels, d_cond, d_rows.get<double>());
+    hipLaunchKernelGGL(k_env_marginal, dim3(1), dim3(256), 0, 0, d_rows.get<const double>(), H, d_marg, d_total.get<double>());
+    HIPCHK(hipGetLastError());
+    double total = 0.0;
+    HIPCHK(hipMemcpy(&total, d_total.get(), sizeof(double), hipMemcpyDeviceToHost));
+    *has = total > 0.0 && std::isfinite(total);
     return HRT_OK;
 }
 
@@ -1990,8 +2105,10 @@ hrt_status launch_wavefront(hrt_scene* sc, const hrt_camera* cam, const hrt_para
     const unsigned n_local = map_pixels(map);
     const int D = pr->max_depth;
     const int n_mesh = (int)sc->mesh_prims.size();
-    // HRT_FLAG_NEE in a scene without table lights is the default render: nothing would differ
-    const bool nee = (pr->flags & HRT_FLAG_NEE) != 0 && sc->n_lights > 0;
+    // HRT_FLAG_NEE in a scene without table lights is the default render: nothing would differ.  HRT_FLAG_NEE_ENV
+    //  without an environment table is HRT_FLAG_NEE.
+    const bool env = (pr->flags & HRT_FLAG_NEE) != 0 && (pr->flags & HRT_FLAG_NEE_ENV) != 0 && sc->env_marg;
+    const bool nee = (pr->flags & HRT_FLAG_NEE) != 0 && (sc->n_lights > 0 || env);
     size_t cap = wf_max_slots(sc, nee);
     const int s_end = s_first + s_count;
     int chunk = (int)std::min<size_t>((size_t)s_count, std::max<size_t>(1, cap / n_local));
@@ -2008,6 +2125,7 @@ hrt_status launch_wavefront(hrt_scene* sc, const hrt_camera* cam, const hrt_para
     if (st != HRT_OK) return st;
     WfBuf w = sc->wf.buf;
     if (nee) { w.lights = sc->d_lights; w.light_of = sc->d_light_of; w.n_lights = sc->n_lights; }
+    if (env) { w.env_marg = sc->env_marg.get<float>(); w.env_cond = sc->env_cond.get<float>(); w.env_w = sc->env_w; w.env_h = sc->env_h; }
     WfScene ws;
     ws.has_mesh = n_mesh > 0;
     ws.first_mesh = n_mesh > 0 ? sc->mesh_prims.front() : sc->n_prims;
@@ -2131,14 +2249,21 @@ hrt_status launch_wavefront(hrt_scene* sc, const hrt_camera* cam, const hrt_para
             }
             next_counters((unsigned)task_blocks * 4u);
             w.ref_prod = ref_block(r + 1, 0); w.ref_cons = ref_block(D, 0);
-            with_bool(nee, [&](auto N) { with_bool(stats, [&](auto S) {
-                hipLaunchKernelGGL((k_wf_shade<decltype(S)::value, decltype(N)::value>), dim3(task_blocks), dim3(256), 0, stream, sc->ds, *pr, map, ws, n_local, s0, r, w,
-                                   sc->d_counters);
-            }); });
+            if (env) {
+                with_bool(stats, [&](auto S) {
+                    hipLaunchKernelGGL((k_wf_shade<decltype(S)::value, true, true>), dim3(task_blocks), dim3(256), 0, stream, sc->ds, *pr, map, ws, n_local, s0, r, w,
+                                       sc->d_counters);
+                });
+            } else {
+                with_bool(nee, [&](auto N) { with_bool(stats, [&](auto S) {
+                    hipLaunchKernelGGL((k_wf_shade<decltype(S)::value, decltype(N)::value>), dim3(task_blocks), dim3(256), 0, stream, sc->ds, *pr, map, ws, n_local, s0, r, w,
+                                       sc->d_counters);
+                }); });
+            }
             if (nee && r + 1 < D) {   // survivors of the last round: none (bounce + 1 < max_depth)
                 // (launches per round with NEE: pre + ext per mesh, stale, shade, shadow <= the 2 * max(1, n_mesh) + 2 of wf_counter_words)
                 next_counters((unsigned)task_blocks * 4u);
-                hipLaunchKernelGGL(k_wf_shadow, dim3(task_blocks), dim3(HRT_BLOCK), 0, stream, sc->ds, *pr, map, n_local, s0, r, w);
+                hipLaunchKernelGGL(env ? k_wf_shadow<true> : k_wf_shadow<false>, dim3(task_blocks), dim3(HRT_BLOCK), 0, stream, sc->ds, *pr, map, n_local, s0, r, w);
             }
             if (progress)   // paths ended so far = earlier batches + this batch's slots - the live ones (w.live, as k_wf_shade left it)
                 hipLaunchKernelGGL(k_wf_progress, dim3(1), dim3(256), 0, stream, w.live, w.n_tasks, sc->progress_base + n_slots, sc->d_progress);
@@ -2416,14 +2541,24 @@ hrt_status hrt_scene_create(const hrt_flat_scene* f, int device, hrt_scene** out
     sc->ds.lprims = d_prims; sc->ds.lmats = d_mats; sc->ds.ltexs = d_texs; sc->ds.lmeshes = d_meshes;
     sc->ds.n_mats = (int32_t)f->n_materials; sc->ds.n_texs = (int32_t)f->n_textures; sc->ds.n_meshes = (int32_t)f->n_meshes;
     sc->n_prims = (int)f->n_prims;
+    {   // HRT_FLAG_NEE_ENV's table of an environment background, from the texels just uploaded
+        const hrt_texture& t = f->textures[f->background_tex];
+        if (t.kind == HRT_TEX_ENV && t.width > 0 && t.height > 0) {
+            DevBuf marg, cond;
+            HRTCHK(marg.alloc(((size_t)t.height + 1) * sizeof(float), "hipMalloc(env table)"));
+            HRTCHK(cond.alloc((size_t)t.height * ((size_t)t.width + 1) * sizeof(float), "hipMalloc(env table)"));
+            bool has = false;
+            HRTCHK(env_table_device(d_f32 + t.offset, t.width, t.height, t.channels, marg.get<float>(), cond.get<float>(), &has));
+            if (has) { sc->env_marg = std::move(marg); sc->env_cond = std::move(cond); sc->env_w = t.width; sc->env_h = t.height; }
+        }
+    }
     {   // HRT_FLAG_NEE's light table
         std::vector<float> lights;
         std::vector<int32_t> light_of;
         sc->n_lights = build_light_table(f, lights, light_of);
-        if (sc->n_lights > 0) {
-            HRTCHK(up(sc->d_lights, lights.data(), lights.size() * sizeof(float)));
-            HRTCHK(up(sc->d_light_of, light_of.data(), light_of.size() * sizeof(int32_t)));
-        }
+        if (sc->n_lights > 0) HRTCHK(up(sc->d_lights, lights.data(), lights.size() * sizeof(float)));
+        // (an environment table alone also renders the NEE instantiations, which look every hit prim up in light_of)
+        if (sc->n_lights > 0 || sc->env_marg) HRTCHK(up(sc->d_light_of, light_of.data(), light_of.size() * sizeof(int32_t)));
     }
     for (uint32_t i = 0; i < f->n_prims; ++i)
         if (f->prims[i].kind == HRT_PRIM_MESH) {
@@ -2684,6 +2819,28 @@ hrt_status hrt_closest_hit(hrt_scene* sc, const hrt_params* pr, int64_t n, const
                        d_h.get<hrt_hit>());
     if ((e = hipGetLastError()) != hipSuccess) return fail_hip(e, "k_closest_hit launch");
     if ((e = hipMemcpy(out, d_h.get(), (size_t)n * sizeof(hrt_hit), hipMemcpyDeviceToHost)) != hipSuccess) return fail_hip(e, "hipMemcpy D2H");
+    return HRT_OK;
+    HRT_API_CATCH
+}
+
+hrt_status hrt_env_table_build(const float* texels, int32_t W, int32_t H, int32_t channels, float* marginal_out, float* conditional_out) {
+    HRT_API_TRY
+    if (!texels || !marginal_out || !conditional_out || W < 1 || H < 1 || channels < 3) return fail(HRT_ERR_INVALID, "bad argument");
+    if ((uint64_t)W * (uint64_t)H * (uint64_t)channels > ((uint64_t)1 << 40)) return fail(HRT_ERR_UNSUPPORTED, "map too large");
+    const size_t n_tex = (size_t)W * (size_t)H * (size_t)channels, n_marg = (size_t)H + 1, n_cond = (size_t)H * ((size_t)W + 1);
+    DevBuf d_tex, d_marg, d_cond;
+    HRTCHK(upload(d_tex, texels, n_tex * sizeof(float)));
+    HRTCHK(d_marg.alloc(n_marg * sizeof(float), "hipMalloc"));
+    HRTCHK(d_cond.alloc(n_cond * sizeof(float), "hipMalloc"));
+    bool has = false;
+    HRTCHK(env_table_device(d_tex.get<float>(), W, H, channels, d_marg.get<float>(), d_cond.get<float>(), &has));
+    if (!has) {
+        std::fill(marginal_out, marginal_out + n_marg, 0.0f);
+        std::fill(conditional_out, conditional_out + n_cond, 0.0f);
+        return HRT_OK;
+    }
+    HIPCHK(hipMemcpy(marginal_out, d_marg.get(), n_marg * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(conditional_out, d_cond.get(), n_cond * sizeof(float), hipMemcpyDeviceToHost));
     return HRT_OK;
     HRT_API_CATCH
 }

@@ -29,14 +29,18 @@ enum rng_purpose : uint32_t {
     RNG_BALL = 3,     // glm::ballRand rejection loop, aux = attempt
     RNG_BUILD = 4,    // bvh.cpp:10 axis choice (oracle tree build only)
     RNG_LENS = 5,     // camera.h:34 glm::circularRand(lensRadius), HRT_FLAG_THIN_LENS only (bounce field = 0)
-    RNG_LIGHT = 6     // HRT_FLAG_NEE only: one draw per eligible vertex (bounce field = the vertex's bounce, aux = 0):
+    RNG_LIGHT = 6,    // HRT_FLAG_NEE only: one draw per eligible vertex (bounce field = the vertex's bounce, aux = 0):
                       //   x = light choice, y / z = the point on the light, w = the root choice (hrt_device.h nee_*)
+    RNG_ENV = 7       // HRT_FLAG_NEE_ENV only: per eligible vertex (bounce field = the vertex's bounce) aux = 0: x = row, y = column,
+                      //   z = phi in the cell, w = cos theta in the cell; aux = 1: x = the root choice (hrt_device.h env_*)
 };
 // Final counter layout: (pixel, sample, bounce, purpose | aux << 8).  The path's own draws (JITTER, LENS, SCATTER, BALL, MEDIUM)
 // use bounce = the segment's index; HRT_FLAG_NEE's shadow ray of the vertex at bounce b draws its ConstantMedium free paths
 // with bounce = b | HRT_RNG_SHADOW (bit 31), so they never share numbers with a path segment's, and RNG_LIGHT is a purpose
 // of its own: every draw of the BSDF path is the one of the default render.
 #define HRT_RNG_SHADOW 0x80000000u
+// HRT_FLAG_NEE_ENV's environment shadow ray of the same vertex: bounce = b | HRT_RNG_SHADOW | HRT_RNG_SHADOW_ENV (bit 30)
+#define HRT_RNG_SHADOW_ENV 0x40000000u
 
 HRT_HD void philox_round(uint32_t& c0, uint32_t& c1, uint32_t& c2, uint32_t& c3, uint32_t k0, uint32_t k1) {
     uint64_t p0 = (uint64_t)0xD2511F53u * c0;

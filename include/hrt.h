@@ -236,13 +236,19 @@ enum {
     HRT_FLAG_THIN_LENS = 1u << 3, /* sample the lens as camera.h:34's commented-out call would (see hrt_camera); off = the reference */
     HRT_FLAG_PROGRESS = 1u << 4, /* keep the host-readable progress counter of hrt_scene_progress / hrt_multi_progress up to date
                                     (the reference's reporter thread, main.cpp:97-109): one tiny launch per round */
-    HRT_FLAG_NEE = 1u << 5      /* next-event estimation (off = the reference's rayColour estimator): at every vertex whose
+    HRT_FLAG_NEE = 1u << 5,     /* next-event estimation (off = the reference's rayColour estimator): at every vertex whose
                                     scatter is Lambertian and whose next segment is traced, one light of the scene's light table (its
                                     unwrapped rects and spheres with a DiffuseLight material) is sampled and a shadow ray traced, and the
                                     result is combined with the BSDF bounce by multiple importance sampling (power heuristic).  The path
                                     itself, and hrt_stats::rays, are those of the default render; the shadow rays are counted in
                                     hrt_stats::shadow_rays.  Wavefront pipeline only: with HRT_FLAG_MEGAKERNEL every render call returns
                                     HRT_ERR_UNSUPPORTED.  A scene without table lights renders as without the flag. */
+    HRT_FLAG_NEE_ENV = 1u << 6  /* with HRT_FLAG_NEE (alone: HRT_ERR_INVALID): also importance-sample the environment map.
+                                    Every eligible vertex takes one more sample, drawn by luminance x solid angle from a table of the
+                                    HRT_TEX_ENV background's texels (built at hrt_scene_create), and traces a second shadow ray that sees
+                                    the sky when it hits nothing; an escaping bounce from such a vertex gets the matching MIS weight.
+                                    Both shadow rays count in hrt_stats::shadow_rays.  A background without a table (not an environment
+                                    map, or one of total weight 0) renders exactly as HRT_FLAG_NEE alone.  Megakernel: HRT_ERR_UNSUPPORTED. */
 };
 
 typedef struct hrt_rect { int32_t x0, y0, w, h; } hrt_rect;   /* y0 = row index from the TOP (pIdx / W) */
@@ -253,7 +259,8 @@ typedef struct hrt_stats {
     uint64_t box_tests;  /* BVH child boxes tested (32 B each)            */
     uint64_t tri_tests;  /* triangles tested (36 B each)                  */
     uint64_t mesh_hits;  /* segments whose closest hit is a mesh triangle (60 B attrs) */
-    uint64_t env_lookups;/* segments that escaped to an fp32 env map (12 B) */
+    uint64_t env_lookups;/* segments that escaped to an fp32 env map (12 B); HRT_FLAG_NEE_ENV's environment shadow rays read the map
+                            too but are not segments: they are counted in shadow_rays only */
     double kernel_ms;    /* path-trace time (megakernel launch, or the whole wavefront pipeline of one render
                             call), summed over `launches`, from HIP events recorded on the launch stream */
     uint64_t launches;   /* render calls (megakernel launches / wavefront pipeline runs) accumulated here */
@@ -435,6 +442,13 @@ hrt_status hrt_closest_hit(hrt_scene* scene, const hrt_params* params, int64_t n
  * check CPU == GPU bit for bit.  op: 0 sin, 1 cos, 2 acos, 3 atan2(x=in, y=in2), 4 log,
  * 5 philox (in = counter words as float bits; out 4 words per input). */
 hrt_status hrt_math_probe(int device, int32_t op, int64_t n, const float* in, const float* in2, float* out);
+
+/* HRT_FLAG_NEE_ENV's sampling table of an environment map, built by the same kernels hrt_scene_create runs, on the current
+ * device, from host memory: texels = W x H x channels fp32 (channels >= 3; rows from the top, as the HRT_TEX_ENV texture stores them).
+ * marginal_out gets H + 1 floats (the CDF over rows), conditional_out H x (W + 1) floats (each row's CDF over its columns).  Every CDF
+ * starts at exactly 0, ends at exactly 1 and is monotone; a row of weight 0 is all 0 but its last entry.  When the map has no table
+ * (total weight 0 or not finite) every entry of both outputs is 0, so marginal_out[H] == 0 says "no table". */
+hrt_status hrt_env_table_build(const float* texels, int32_t W, int32_t H, int32_t channels, float* marginal_out, float* conditional_out);
 
 /* Debug entry: a library built with -DHRT_DEBUG_BOUNDS checks every table index a hit record is built from (triangle of a mesh,
  * prim, material, texture, mesh, frontFace source) against its table, counts the violations per kind and carries on with index 0
