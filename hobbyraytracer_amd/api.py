@@ -33,6 +33,7 @@ MAX_XFORMS = 4
 Q1_ROTQ_NORMALIZE, Q2_TRI_NO_TMIN, Q3_TRI_NO_FACE, Q4_SHEAR_FROM_ORIGIN = 1, 2, 4, 8
 QUIRKS_REFERENCE, QUIRKS_FIXED = 0xF, 0x0
 FLAG_STATS, FLAG_MEGAKERNEL, FLAG_TIMING, FLAG_THIN_LENS, FLAG_PROGRESS, FLAG_NEE, FLAG_NEE_ENV = 1, 2, 4, 8, 16, 32, 64
+FLAG_NEE_EMITTERS = 128
 
 
 # ---------------------------------------------------------------- structs (hrt.h)
@@ -133,7 +134,8 @@ HIP_SYMBOLS = ["hrt_device_count", "hrt_scene_create", "hrt_scene_destroy", "hrt
                "hrt_resolve_u8_device", "hrt_closest_hit", "hrt_math_probe", "hrt_status_str", "hrt_last_error", "hrt_version",
                "hrt_multi_create", "hrt_multi_destroy", "hrt_multi_devices", "hrt_multi_uses_rccl", "hrt_multi_render", "hrt_bvh_build_device", "hrt_bvh_build_sah",
                "hrt_debug_bounds_violations", "hrt_scene_progress", "hrt_multi_progress",
-               "hrt_render_stripes_adaptive_device", "hrt_render_stripes_adaptive", "hrt_adaptive_mean_device", "hrt_env_table_build"]
+               "hrt_render_stripes_adaptive_device", "hrt_render_stripes_adaptive", "hrt_adaptive_mean_device", "hrt_env_table_build",
+               "hrt_emitter_table_build"]
 HOST_SYMBOLS = ["hrt_host_load_yaml", "hrt_host_free", "hrt_host_flat", "hrt_host_film", "hrt_host_camera", "hrt_host_bvh_depth",
                 "hrt_default_params", "hrt_asset_write_teapot_obj", "hrt_asset_write_bust_obj", "hrt_asset_write_hall_hdr",
                 "hrt_host_write_image", "hrt_host_read_hdr", "hrt_host_read_png", "hrt_host_read_jpeg", "hrt_host_write_hdr", "hrt_host_write_pfm", "hrt_host_read_pfm", "hrt_host_last_error", "hrt_host_set_bvh_builder"]
@@ -191,6 +193,7 @@ _hip.hrt_multi_uses_rccl.restype = C.c_int32
 _hip.hrt_multi_render.argtypes = [_vp, C.POINTER(Camera), C.POINTER(Params), C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _u8p, C.POINTER(Stats)]
 _hip.hrt_math_probe.argtypes = [C.c_int, C.c_int32, C.c_int64, _fp, _fp, _fp]
 _hip.hrt_env_table_build.argtypes = [_fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp]
+_hip.hrt_emitter_table_build.argtypes = [_vp, C.POINTER(C.c_int64), _fp, _fp, _fp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
 
 _host.hrt_host_last_error.restype = C.c_char_p
 _host.hrt_host_load_yaml.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(_vp)]
@@ -238,9 +241,11 @@ def _ptr(a, t=_fp):
 
 # ---------------------------------------------------------------- host side
 def default_params(width, height, samples, quirks=QUIRKS_REFERENCE, seed=0, max_depth=50, stats=False, megakernel=False, timing=False,
-                   thin_lens=False, progress=False, nee=False, nee_env=False):
+                   thin_lens=False, progress=False, nee=False, nee_env=False, nee_emitters=False):
     """nee: next-event estimation with MIS for the scene's rect and sphere lights (FLAG_NEE).
-    nee_env: also importance-sample the environment map (FLAG_NEE_ENV); implies nee."""
+    nee_env: also importance-sample the environment map (FLAG_NEE_ENV); implies nee.
+    nee_emitters: sample every rect, box and mesh emitter, wrapped or not, by an alias table (FLAG_NEE_EMITTERS, DESIGN.md 4.7);
+    implies nee."""
     p = Params()
     _host.hrt_default_params(C.byref(p), width, height, samples)
     p.quirks = quirks
@@ -248,7 +253,8 @@ def default_params(width, height, samples, quirks=QUIRKS_REFERENCE, seed=0, max_
     p.seed_hi = (seed >> 32) & 0xFFFFFFFF
     p.max_depth = max_depth
     p.flags = (FLAG_STATS if stats else 0) | (FLAG_MEGAKERNEL if megakernel else 0) | (FLAG_TIMING if timing else 0) | \
-              (FLAG_THIN_LENS if thin_lens else 0) | (FLAG_PROGRESS if progress else 0) | (FLAG_NEE if nee or nee_env else 0) | (FLAG_NEE_ENV if nee_env else 0)
+              (FLAG_THIN_LENS if thin_lens else 0) | (FLAG_PROGRESS if progress else 0) | (FLAG_NEE if nee or nee_env or nee_emitters else 0) | \
+              (FLAG_NEE_ENV if nee_env else 0) | (FLAG_NEE_EMITTERS if nee_emitters else 0)
     return p
 
 
@@ -410,6 +416,28 @@ def env_table_build(texels):
     cond = np.zeros((H, W + 1), np.float32)
     _check(_hip.hrt_env_table_build(_ptr(t), W, H, ch, _ptr(marg), _ptr(cond)))
     return None if marg[H] == 0.0 else (marg, cond)
+
+
+def emitter_table_build(flat_ptr):
+    """FLAG_NEE_EMITTERS' emitter table of a flattened scene (hrt_emitter_table_build), host only.  Returns a dict of
+    numpy arrays: rec [n, 16] fp32 (the 4 float4 of hrt_emitters.h), shade [n, 4] fp32, thresh [n] fp32, alias [n] int32, base
+    [n_prims] int32, plus the record fields prim, kind, sub (int32) and p_sel (fp32); n = 0 when the scene has no table."""
+    n = C.c_int64(0)
+    _check(_hip.hrt_emitter_table_build(flat_ptr, C.byref(n), None, None, None, None, None))
+    n_prims = C.cast(flat_ptr, C.POINTER(FlatScene)).contents.n_prims
+    k = max(1, n.value)
+    rec = np.zeros((k, 16), np.float32)
+    shade = np.zeros((k, 4), np.float32)
+    thresh = np.zeros(k, np.float32)
+    alias = np.zeros(k, np.int32)
+    base = np.zeros(max(1, n_prims), np.int32)
+    _check(_hip.hrt_emitter_table_build(flat_ptr, C.byref(n), _ptr(rec), _ptr(shade), _ptr(thresh), _ptr(alias, C.POINTER(C.c_int32)),
+                                        _ptr(base, C.POINTER(C.c_int32))))
+    m = n.value
+    rec, shade, thresh, alias, base = rec[:m], shade[:m], thresh[:m], alias[:m], base[:n_prims]
+    bits = rec.view(np.int32)
+    return {"rec": rec, "shade": shade, "thresh": thresh, "alias": alias, "base": base,
+            "prim": bits[:, 0].copy(), "kind": bits[:, 1].copy(), "p_sel": rec[:, 2].copy(), "sub": bits[:, 3].copy()}
 
 
 def stripe_rows(height, rows_per_block, rank, n_ranks):

@@ -12,6 +12,7 @@
 #pragma once
 #include "hrt_rng.h"
 #include "../../include/hrt.h"
+#include "hrt_emitters.h"
 
 namespace hrt {
 
@@ -1375,6 +1376,50 @@ __device__ inline int nee_choose(P L, int n_lights, uint32_t u) {
 __device__ inline vec3 nee_emitted(const DScene& sc, const DRec& rec) {
     const hrt_material& m = sc.lmats[rec.mat];
     return matvec3_value(sc, m.albedo, rec.u, rec.v, rec.p) * matscalar_value(sc, m.s0, rec.u, rec.v, rec.p);
+}
+
+// ------------------------------------------------------------------ emitter-table sampling (HRT_FLAG_NEE_EMITTERS)
+// The table is hrt_emitters.h's (HRT_EMIT_REC float4 per entry, a shade-side float4 per entry, an alias table of (thresh, alias bits)).
+// Alias choice from RNG_LIGHT aux 0 word x (the slot, (uint64)x n >> 32) and aux 1 word x (the coin).
+template <class P>
+__device__ inline int emit_choose(P tab, int n, uint32_t ux, uint32_t coin) {
+    const int s = (int)(((uint64_t)ux * (uint64_t)(uint32_t)n) >> 32);
+    const auto a = tab[s];                 // (thresh, alias bits)
+    return u01(coin) < a.x ? s : __float_as_int(a.y);
+}
+// A uniform point y of a planar entry (E1 = origin, area; E2, E3 = the edges), tri: the triangle (o, o + e1, o + e2) by the
+// square-root parametrisation, else the parallelogram; w = its direction from x, pl = dist^2 / (A |n.w|) (emission is two-sided:
+// material_scatter's DiffuseLight branch has no frontFace test), reach = dist.  false: no direction.
+__device__ inline bool emit_sample_planar(bool tri, float4 E1, float4 E2, float4 E3, vec3 x, uint32_t uy, uint32_t uz, vec3& w, float& pl,
+                                          float& reach) {
+    const vec3 o(E1.x, E1.y, E1.z), e1(E2.x, E2.y, E2.z), e2(E3.x, E3.y, E3.z);
+    float a = u01(uy), b = u01(uz);
+    if (tri) { const float s = sqrtf(a); a = s * (1.0f - b); b = s * b; }
+    const vec3 y = o + a * e1 + b * e2;
+    const vec3 dl = y - x;
+    const float d2 = dot(dl, dl), dist = sqrtf(d2);
+    if (!(dist > 0.0f)) return false;
+    w = dl / dist;
+    const float cl = fabsf(dot(w, normalize(cross(e1, e2))));
+    pl = d2 / (E1.w * cl);
+    reach = dist;
+    return cl > 0.0f && pl < 3.0e38f;
+}
+// The same density from the direction alone, times P_sel: q of the unit direction w from x that meets a planar entry at y, from its
+// shade-side record S = (unit normal, P_sel / A).  0 for an entry of weight 0.
+__device__ inline float emit_q_planar(float4 S, vec3 x, vec3 w, vec3 y) {
+    const vec3 dl = y - x;
+    const float cl = fabsf(dot(w, vec3(S.x, S.y, S.z)));
+    return cl > 0.0f ? S.w * dot(dl, dl) / cl : 0.0f;
+}
+// nee_pdf of a sphere entry from its shade-side record S = (centre, -r)
+__device__ inline float emit_pdf_sphere(float4 S, vec3 x, vec3 w, vec3 y) {
+    const float r = -S.w;
+    float4 L0, L1, L2;
+    L0.x = 0.0f; L0.y = __int_as_float(HRT_PRIM_SPHERE); L0.z = 0.0f; L0.w = 0.0f;
+    L1.x = S.x; L1.y = S.y; L1.z = S.z; L1.w = r;
+    L2.x = 0.0f; L2.y = 4.0f * HRT_NEE_PI * r * r; L2.z = 0.0f; L2.w = 0.0f;
+    return nee_pdf(L0, L1, L2, x, w, y);
 }
 
 // main.cpp:47-58

@@ -15,6 +15,7 @@
 //   k_ad_select / k_ad_scan / k_wf_reduce_list / k_ad_mean   adaptive sampling.
 //   k_wf_shade<STATS, true> / k_wf_shadow<false>   next-event estimation with MIS, HRT_FLAG_NEE.
 //   k_wf_shade<STATS, true, true> / k_wf_shadow<true> / k_env_rows / k_env_marginal   environment-map sampling, HRT_FLAG_NEE_ENV (4.6).
+//   k_wf_shade<STATS, true, ENV, true> / k_wf_shadow<ENV, true>   the emitter table, HRT_FLAG_NEE_EMITTERS (4.7).
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>   // types and prototypes only: the library is loaded on demand (rccl_api below)
 #include <dlfcn.h>
@@ -337,6 +338,12 @@ struct WfBuf {
     const float* env_marg;
     const float* env_cond;
     int env_w, env_h;
+    // HRT_FLAG_NEE_EMITTERS only: the emitter table (hrt_emitters.h), n_emit entries
+    const float4* emit_rec;      // HRT_EMIT_REC float4 per entry (k_wf_shadow)
+    const float4* emit_shade;    // per entry: unit normal, P_sel / A (planar) or -1 in w (sphere: emit_rec) (k_wf_shade)
+    const float2* emit_alias;    // per slot: threshold, alias entry (bits)
+    const int32_t* emit_base;    // per prim: its first entry, -1 if it has none (an entry = base + triangle index or box side)
+    int n_emit;
 };
 // Task ownership.  Tasks differ in cost by orders of magnitude (a run of pixels under the mesh vs. a run of sky), so a
 // static wave -> task map leaves most waves idle while a few finish: plain striding (task = wave + i * n_waves) even
@@ -1053,7 +1060,9 @@ __device__ inline void missq_flush(const DScene& sc, const WfBuf& w, MissQueue& 
 // HRT_FLAG_NEE: path_shade plus the multiple-importance weight of an emission that a bounce from an eligible vertex finds on a
 // table light (prev_pb = that vertex's p_b of the direction, -1: not eligible), and the record k_wf_shadow and the next round
 // read (nrec: shading normal, p_b of the new direction or -1).  The light sample itself is k_wf_shadow's.
-template <bool STATS>
+// EMIT (HRT_FLAG_NEE_EMITTERS): the light is an entry of the emitter table, emit_base[prim] + the hit's triangle
+// index (through sub_tri) or box side; q from its shade-side record.
+template <bool STATS, bool EMIT = false>
 __device__ HRT_WAVE_FN bool path_shade_nee(const DScene& sc, const hrt_params& pr, const WfBuf& w, const rng_ctx& ctx, PathState& ps,
                                            const WorldHit& wh, PathCounters& pc, float prev_pb, float4& nrec) {
     if (STATS && sc.lprims[wh.prim].kind == HRT_PRIM_MESH) pc.mesh_hits++;
@@ -1062,7 +1071,19 @@ __device__ HRT_WAVE_FN bool path_shade_nee(const DScene& sc, const hrt_params& p
     vec3 emitted, attenuation, so, sd;
     bool lambert = false;
     const bool b = material_scatter(sc, rec, ps.d, ctx, emitted, attenuation, so, sd, &lambert);
-    if (!b && prev_pb >= 0.0f) {
+    if (EMIT && !b && prev_pb >= 0.0f) {
+        int li = w.emit_base[wh.prim];
+        if (li >= 0) {
+            if (wh.sub >= 0) li += sub_tri(wh.sub);
+            const float4 S = w.emit_shade[li];
+            const vec3 wn = normalize(ps.d);
+            float q;
+            if (S.w >= 0.0f) q = emit_q_planar(S, ps.o, wn, rec.p);
+            else            // an unwrapped sphere (S = centre, -r): the HRT_FLAG_NEE density times its P_sel
+                q = w.emit_rec[HRT_EMIT_REC * li].z * emit_pdf_sphere(S, ps.o, wn, rec.p);
+            emitted = emitted * nee_mis_bsdf(prev_pb, q);
+        }
+    } else if (!b && prev_pb >= 0.0f) {
         const int li = w.light_of[wh.prim];
         if (li >= 0) {   // q from the ray's origin to the hit: the density the light strategy gives this direction
             const float4 L0 = w.lights[HRT_NEE_REC * li], L1 = w.lights[HRT_NEE_REC * li + 1], L2 = w.lights[HRT_NEE_REC * li + 2];
@@ -1084,7 +1105,7 @@ __device__ HRT_WAVE_FN bool path_shade_nee(const DScene& sc, const hrt_params& p
     return ps.bounce >= pr.max_depth;
 }
 
-template <bool STATS, bool NEE = false, bool ENV = false>
+template <bool STATS, bool NEE = false, bool ENV = false, bool EMIT = false>
 __device__ HRT_WAVE_FN void wf_shade_task(const DScene& sc, const hrt_params& pr, const RenderMap& map, const WfScene& ws, unsigned n_local, int s0, int round,
                                      const WfBuf& w, unsigned task, unsigned n, unsigned lane, unsigned long long lt, MissQueue& mq,
                                      PathCounters& pc, unsigned& n_seg, unsigned& n_culled, unsigned& live_out, unsigned& qn_out, unsigned& rn_out) {
@@ -1136,7 +1157,8 @@ __device__ HRT_WAVE_FN void wf_shade_task(const DScene& sc, const hrt_params& pr
         float4 nrec = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
         if (j0 + lane < n && !missed) {
             bool ended;
-            if (ENV) ended = path_shade_nee<STATS>(sc, pr, w, ctx, ps, wh, pc, prev_pb, nrec);
+            if (ENV) ended = path_shade_nee<STATS, EMIT>(sc, pr, w, ctx, ps, wh, pc, prev_pb, nrec);
+            else if (EMIT) ended = path_shade_nee<STATS, true>(sc, pr, w, ctx, ps, wh, pc, round > 0 ? w.N[par][pos].w : -1.0f, nrec);
             else if (NEE) ended = path_shade_nee<STATS>(sc, pr, w, ctx, ps, wh, pc, round > 0 ? w.N[par][pos].w : -1.0f, nrec);
             else ended = path_shade<STATS>(sc, pr, ctx, ps, wh, pc);
             if (ended) w.rad[slot] = make_float4(ps.result.x, ps.result.y, ps.result.z, 0.0f);
@@ -1191,7 +1213,8 @@ __device__ HRT_WAVE_FN void wf_shade_counters(const WfBuf& w, DeviceCounters* co
 #define HRT_SHADE_WAVES 4   // waves per SIMD the register allocator must leave room for (<= 128 VGPRs)
 #endif
 // ENV (HRT_FLAG_NEE_ENV, with NEE only): the environment map's MIS weight on escapes from eligible vertices
-template <bool STATS, bool NEE, bool ENV = false>
+// EMIT (HRT_FLAG_NEE_EMITTERS, with NEE only): the MIS weight of emission found on any entry of the emitter table
+template <bool STATS, bool NEE, bool ENV = false, bool EMIT = false>
 __global__ __launch_bounds__(256, HRT_SHADE_WAVES) void k_wf_shade(DScene sc, hrt_params pr, RenderMap map, WfScene ws, unsigned n_local, int s0, int round,
                                                   WfBuf w, DeviceCounters* counters) {
     const unsigned lane = threadIdx.x & 63u;
@@ -1209,7 +1232,7 @@ __global__ __launch_bounds__(256, HRT_SHADE_WAVES) void k_wf_shade(DScene sc, hr
     PathCounters pc; pc.rays = 0; pc.samples = 0; pc.mesh_hits = 0; pc.env_lookups = 0; pc.bvh.box_tests = 0; pc.bvh.tri_tests = 0;
     HRT_FOR_MY_TASKS(task, w, wave, lane) {
         unsigned live, qn, rn;
-        wf_shade_task<STATS, NEE, ENV>(sc, pr, map, ws, n_local, s0, round, w, task, HRT_UNIFORM(w.live[task]), lane, lt, mq, pc, n_seg, n_culled, live, qn, rn);
+        wf_shade_task<STATS, NEE, ENV, EMIT>(sc, pr, map, ws, n_local, s0, round, w, task, HRT_UNIFORM(w.live[task]), lane, lt, mq, pc, n_seg, n_culled, live, qn, rn);
         if (lane == 0) { w.live[task] = live; w.qn[task] = qn; w.rn[task] = rn; if (rn) wf_ref_publish(w, task, rn); }
     }
     if (mq.count) missq_flush<STATS, ENV>(sc, w, mq, lane, mq.count, pc);
@@ -1229,8 +1252,14 @@ __global__ __launch_bounds__(256, HRT_SHADE_WAVES) void k_wf_shade(DScene sc, hr
 // environment sample: a direction from one RNG_ENV draw (env_sample), the ray d = t_k w with t_max = inf that sees the sky when
 // world_hit misses (media: bounce field round | HRT_RNG_SHADOW | HRT_RNG_SHADOW_ENV), and the term atten background pb p_env /
 // (pb^2 + p_env^2), added to `direct` after the table-light term.
+// EMIT (HRT_FLAG_NEE_EMITTERS): the light is an entry of the emitter table, chosen by its alias table (slot from word x of
+// RNG_LIGHT aux 0, coin from word x of aux 1); a planar entry is sampled uniformly over its world-space area (y, z of aux 0), a sphere as
+// HRT_FLAG_NEE does.  The sample is seen exactly when world_hit's closest hit is the entry's prim AND, for a mesh or a box, its sub is the
+// entry's triangle or side.  t_max: reach / t_k x 1.001 for an unwrapped entry; inf under a wrapper, whose child measures t in its own
+// units (quirk Q-1).  -DHRT_EMIT_EUCLID_TMAX (experiment only): the Euclidean cut for wrapped entries too -- kept
+// compilable so the unbiasedness test can be shown to catch it.
 #define HRT_SHADOWQ_CAP 128
-template <bool ENV>
+template <bool ENV, bool EMIT = false>
 __global__ __launch_bounds__(HRT_BLOCK) void k_wf_shadow(DScene sc, hrt_params pr, RenderMap map, unsigned n_local, int s0, int round, WfBuf w) {
     __shared__ int s_stack[HRT_STACK_DEPTH * HRT_BLOCK];
     __shared__ __attribute__((aligned(16))) uint32_t s_tables[HRT_TABLE_LDS_BYTES / 4];
@@ -1276,9 +1305,41 @@ __global__ __launch_bounds__(HRT_BLOCK) void k_wf_shadow(DScene sc, hrt_params p
         const unsigned slot = __float_as_uint(w.S2[nxt][pos].w);
         const vec3 x(a.x, a.y, a.z);
         [&]() {   // the table-light sample (a lambda: `return` ends it, and the environment sample below still runs)
-            if (ENV && w.n_lights == 0) return;
+            if (ENV && (EMIT ? w.n_emit : w.n_lights) == 0) return;
             rng_ctx ctx = slot_ctx(pr, map, slot, n_local, s0, round);
             const u32x4 u = rng_draw(ctx, RNG_LIGHT, 0);
+            if (EMIT) {
+                const int li = emit_choose(w.emit_alias, w.n_emit, u.x, rng_draw(ctx, RNG_LIGHT, 1).x);
+                const float4 E0 = w.emit_rec[HRT_EMIT_REC * li], E1 = w.emit_rec[HRT_EMIT_REC * li + 1], E2 = w.emit_rec[HRT_EMIT_REC * li + 2];
+                vec3 wd;
+                float pl, reach;
+                const int kind = __float_as_int(E0.y);
+                const bool ok = kind == HRT_PRIM_SPHERE ? nee_sample(E0, E1, E2, x, u.y, u.z, wd, pl, reach)
+                                                        : emit_sample_planar(kind == HRT_EMIT_TRI, E1, E2, w.emit_rec[HRT_EMIT_REC * li + 3], x, u.y, u.z, wd, pl, reach);
+                if (!ok) return;
+                float t0, t1;
+                const float pb = nee_bsdf_pdf(vec3(nr.x, nr.y, nr.z), wd, t0, t1);
+                if (!(pb > 0.0f)) return;
+                const float tk = nee_pick_root(t0, t1, u.w);
+                const vec3 d = tk * wd;
+#ifdef HRT_EMIT_EUCLID_TMAX
+                const float t_max = reach / tk * 1.001f;
+#else
+                const float t_max = E2.w != 0.0f ? __builtin_huge_valf() : reach / tk * 1.001f;   // E2.w: wrapped
+#endif
+                ctx.bounce = (uint32_t)round | HRT_RNG_SHADOW;
+                ++n_shadow;
+                DCounters cnt; cnt.box_tests = 0; cnt.tri_tests = 0;
+                const WorldHit wh = world_hit<false>(sc, x, d, pr.t_min, t_max, pr.quirks, ctx, stack, cnt);
+                const int esub = __float_as_int(E0.w);
+                if (wh.prim != __float_as_int(E0.x) || (esub >= 0 && sub_tri(wh.sub) != esub)) return;
+                DRec rec;
+                hit_record(sc, wh, x, d, pr.quirks, pr.t_min, rec);
+                const vec3 term = vec3(b.z, b.w, az) * nee_emitted(sc, rec) * nee_mis_shadow(pb, E0.z * pl);
+                const float4 acc = w.direct[slot];
+                w.direct[slot] = make_float4(acc.x + term.x, acc.y + term.y, acc.z + term.z, 0.0f);
+                return;
+            }
             const int li = nee_choose(w.lights, w.n_lights, u.x);
             const float4 L0 = w.lights[HRT_NEE_REC * li], L1 = w.lights[HRT_NEE_REC * li + 1], L2 = w.lights[HRT_NEE_REC * li + 2];
             vec3 wd;
@@ -1762,6 +1823,9 @@ struct hrt_scene {
     // HRT_FLAG_NEE_ENV: the environment background's sampling table, built at hrt_scene_create; empty: no table
     DevBuf env_marg, env_cond;
     int env_w = 0, env_h = 0;
+    // HRT_FLAG_NEE_EMITTERS: the emitter table (hrt_emitters.h), built at hrt_scene_create; n_emit = 0: no table
+    DevBuf emit_rec, emit_shade, emit_alias, emit_base;
+    int n_emit = 0;
 };
 
 namespace {
@@ -1969,6 +2033,7 @@ hrt_status check_params(const hrt_params* p) {
     if (p->max_depth > 65536) return fail(HRT_ERR_UNSUPPORTED, "max_depth above 65536 (the reference's is 50, main.cpp:32)");
     if (!(p->t_min == p->t_min)) return fail(HRT_ERR_INVALID, "t_min is NaN");
     if ((p->flags & HRT_FLAG_NEE_ENV) && !(p->flags & HRT_FLAG_NEE)) return fail(HRT_ERR_INVALID, "HRT_FLAG_NEE_ENV needs HRT_FLAG_NEE");
+    if ((p->flags & HRT_FLAG_NEE_EMITTERS) && !(p->flags & HRT_FLAG_NEE)) return fail(HRT_ERR_INVALID, "HRT_FLAG_NEE_EMITTERS needs HRT_FLAG_NEE");
     if ((p->flags & HRT_FLAG_MEGAKERNEL) && (p->flags & HRT_FLAG_NEE)) return fail(HRT_ERR_UNSUPPORTED, "next-event estimation renders on the wavefront pipeline only");
     return HRT_OK;
 }
@@ -2108,7 +2173,10 @@ hrt_status launch_wavefront(hrt_scene* sc, const hrt_camera* cam, const hrt_para
     // HRT_FLAG_NEE in a scene without table lights is the default render: nothing would differ.  HRT_FLAG_NEE_ENV
     //  without an environment table is HRT_FLAG_NEE.
     const bool env = (pr->flags & HRT_FLAG_NEE) != 0 && (pr->flags & HRT_FLAG_NEE_ENV) != 0 && sc->env_marg;
-    const bool nee = (pr->flags & HRT_FLAG_NEE) != 0 && (sc->n_lights > 0 || env);
+    // HRT_FLAG_NEE_EMITTERS samples the emitter table instead of the light table.  Without an emitter table the scene has
+    // no table light either (the emitter table holds every one), so it renders as HRT_FLAG_NEE (or HRT_FLAG_NEE_ENV) would.
+    const bool emit = (pr->flags & HRT_FLAG_NEE) != 0 && (pr->flags & HRT_FLAG_NEE_EMITTERS) != 0 && sc->n_emit > 0;
+    const bool nee = (pr->flags & HRT_FLAG_NEE) != 0 && (sc->n_lights > 0 || env || emit);
     size_t cap = wf_max_slots(sc, nee);
     const int s_end = s_first + s_count;
     int chunk = (int)std::min<size_t>((size_t)s_count, std::max<size_t>(1, cap / n_local));
@@ -2126,6 +2194,10 @@ hrt_status launch_wavefront(hrt_scene* sc, const hrt_camera* cam, const hrt_para
     WfBuf w = sc->wf.buf;
     if (nee) { w.lights = sc->d_lights; w.light_of = sc->d_light_of; w.n_lights = sc->n_lights; }
     if (env) { w.env_marg = sc->env_marg.get<float>(); w.env_cond = sc->env_cond.get<float>(); w.env_w = sc->env_w; w.env_h = sc->env_h; }
+    if (emit) {
+        w.emit_rec = sc->emit_rec.get<const float4>(); w.emit_shade = sc->emit_shade.get<const float4>();
+        w.emit_alias = sc->emit_alias.get<const float2>(); w.emit_base = sc->emit_base.get<const int32_t>(); w.n_emit = sc->n_emit;
+    }
     WfScene ws;
     ws.has_mesh = n_mesh > 0;
     ws.first_mesh = n_mesh > 0 ? sc->mesh_prims.front() : sc->n_prims;
@@ -2249,7 +2321,12 @@ hrt_status launch_wavefront(hrt_scene* sc, const hrt_camera* cam, const hrt_para
             }
             next_counters((unsigned)task_blocks * 4u);
             w.ref_prod = ref_block(r + 1, 0); w.ref_cons = ref_block(D, 0);
-            if (env) {
+            if (emit) {
+                with_bool(env, [&](auto E) { with_bool(stats, [&](auto S) {
+                    hipLaunchKernelGGL((k_wf_shade<decltype(S)::value, true, decltype(E)::value, true>), dim3(task_blocks), dim3(256), 0, stream, sc->ds, *pr, map, ws,
+                                       n_local, s0, r, w, sc->d_counters);
+                }); });
+            } else if (env) {
                 with_bool(stats, [&](auto S) {
                     hipLaunchKernelGGL((k_wf_shade<decltype(S)::value, true, true>), dim3(task_blocks), dim3(256), 0, stream, sc->ds, *pr, map, ws, n_local, s0, r, w,
                                        sc->d_counters);
@@ -2263,7 +2340,10 @@ hrt_status launch_wavefront(hrt_scene* sc, const hrt_camera* cam, const hrt_para
             if (nee && r + 1 < D) {   // survivors of the last round: none (bounce + 1 < max_depth)
                 // (launches per round with NEE: pre + ext per mesh, stale, shade, shadow <= the 2 * max(1, n_mesh) + 2 of wf_counter_words)
                 next_counters((unsigned)task_blocks * 4u);
-                hipLaunchKernelGGL(env ? k_wf_shadow<true> : k_wf_shadow<false>, dim3(task_blocks), dim3(HRT_BLOCK), 0, stream, sc->ds, *pr, map, n_local, s0, r, w);
+                if (emit)
+                    hipLaunchKernelGGL((env ? k_wf_shadow<true, true> : k_wf_shadow<false, true>), dim3(task_blocks), dim3(HRT_BLOCK), 0, stream, sc->ds, *pr, map, n_local, s0, r, w);
+                else
+                    hipLaunchKernelGGL(env ? k_wf_shadow<true> : k_wf_shadow<false>, dim3(task_blocks), dim3(HRT_BLOCK), 0, stream, sc->ds, *pr, map, n_local, s0, r, w);
             }
             if (progress)   // paths ended so far = earlier batches + this batch's slots - the live ones (w.live, as k_wf_shade left it)
                 hipLaunchKernelGGL(k_wf_progress, dim3(1), dim3(256), 0, stream, w.live, w.n_tasks, sc->progress_base + n_slots, sc->d_progress);
@@ -2560,6 +2640,18 @@ hrt_status hrt_scene_create(const hrt_flat_scene* f, int device, hrt_scene** out
         // (an environment table alone also renders the NEE instantiations, which look every hit prim up in light_of)
         if (sc->n_lights > 0 || sc->env_marg) HRTCHK(up(sc->d_light_of, light_of.data(), light_of.size() * sizeof(int32_t)));
     }
+    {   // HRT_FLAG_NEE_EMITTERS' emitter table (hrt_emitters.h): the same host-built bits on every device of a session
+        hrt_emitter_table t;
+        if (hrt_build_emitter_table(f, t) > 0) {
+            std::vector<float> alias(2 * (size_t)t.n);
+            for (int64_t i = 0; i < t.n; ++i) { alias[2 * i] = t.thresh[i]; memcpy(&alias[2 * i + 1], &t.alias[i], 4); }
+            HRTCHK(upload(sc->emit_rec, t.rec.data(), t.rec.size() * sizeof(float)));
+            HRTCHK(upload(sc->emit_shade, t.shade.data(), t.shade.size() * sizeof(float)));
+            HRTCHK(upload(sc->emit_alias, alias.data(), alias.size() * sizeof(float)));
+            HRTCHK(upload(sc->emit_base, t.base.data(), t.base.size() * sizeof(int32_t)));
+            sc->n_emit = (int)t.n;
+        }
+    }
     for (uint32_t i = 0; i < f->n_prims; ++i)
         if (f->prims[i].kind == HRT_PRIM_MESH) {
             sc->mesh_prims.push_back((int)i);
@@ -2841,6 +2933,27 @@ hrt_status hrt_env_table_build(const float* texels, int32_t W, int32_t H, int32_
     }
     HIPCHK(hipMemcpy(marginal_out, d_marg.get(), n_marg * sizeof(float), hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(conditional_out, d_cond.get(), n_cond * sizeof(float), hipMemcpyDeviceToHost));
+    return HRT_OK;
+    HRT_API_CATCH
+}
+
+hrt_status hrt_emitter_table_build(const hrt_flat_scene* flat, int64_t* n_entries, float* records_out, float* shade_out, float* thresh_out,
+                                   int32_t* alias_out, int32_t* base_out) {
+    HRT_API_TRY
+    if (!flat || !n_entries || (flat->n_prims && !flat->prims)) return fail(HRT_ERR_INVALID, "bad argument");
+    hrt_emitter_table t;
+    const int64_t n = hrt_build_emitter_table(flat, t);
+    const bool fill = records_out || shade_out || thresh_out || alias_out || base_out;
+    if (fill) {
+        if (!records_out || !shade_out || !thresh_out || !alias_out || !base_out) return fail(HRT_ERR_INVALID, "fill needs every output");
+        if (*n_entries != n) return fail(HRT_ERR_INVALID, "n_entries is not the table's size");
+        std::copy(t.rec.begin(), t.rec.end(), records_out);
+        std::copy(t.shade.begin(), t.shade.end(), shade_out);
+        std::copy(t.thresh.begin(), t.thresh.end(), thresh_out);
+        std::copy(t.alias.begin(), t.alias.end(), alias_out);
+        std::copy(t.base.begin(), t.base.end(), base_out);
+    }
+    *n_entries = n;
     return HRT_OK;
     HRT_API_CATCH
 }

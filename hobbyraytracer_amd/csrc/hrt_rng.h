@@ -31,6 +31,8 @@ enum rng_purpose : uint32_t {
     RNG_LENS = 5,     // camera.h:34 glm::circularRand(lensRadius), HRT_FLAG_THIN_LENS only (bounce field = 0)
     RNG_LIGHT = 6,    // HRT_FLAG_NEE only: one draw per eligible vertex (bounce field = the vertex's bounce, aux = 0):
                       //   x = light choice, y / z = the point on the light, w = the root choice (hrt_device.h nee_*)
+                      //   HRT_FLAG_NEE_EMITTERS (hrt_device.h emit_*): aux 0 keeps these words, x = the alias slot
+                      //   ((uint64)x n >> 32); aux 1 word x = the alias coin (its y, z, w are unused)
     RNG_ENV = 7       // HRT_FLAG_NEE_ENV only: per eligible vertex (bounce field = the vertex's bounce) aux = 0: x = row, y = column,
                       //   z = phi in the cell, w = cos theta in the cell; aux = 1: x = the root choice (hrt_device.h env_*)
 };

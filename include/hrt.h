@@ -243,12 +243,20 @@ enum {
                                     itself, and hrt_stats::rays, are those of the default render; the shadow rays are counted in
                                     hrt_stats::shadow_rays.  Wavefront pipeline only: with HRT_FLAG_MEGAKERNEL every render call returns
                                     HRT_ERR_UNSUPPORTED.  A scene without table lights renders as without the flag. */
-    HRT_FLAG_NEE_ENV = 1u << 6  /* with HRT_FLAG_NEE (alone: HRT_ERR_INVALID): also importance-sample the environment map.
+    HRT_FLAG_NEE_ENV = 1u << 6, /* with HRT_FLAG_NEE (alone: HRT_ERR_INVALID): also importance-sample the environment map.
                                     Every eligible vertex takes one more sample, drawn by luminance x solid angle from a table of the
                                     HRT_TEX_ENV background's texels (built at hrt_scene_create), and traces a second shadow ray that sees
                                     the sky when it hits nothing; an escaping bounce from such a vertex gets the matching MIS weight.
                                     Both shadow rays count in hrt_stats::shadow_rays.  A background without a table (not an environment
                                     map, or one of total weight 0) renders exactly as HRT_FLAG_NEE alone.  Megakernel: HRT_ERR_UNSUPPORTED. */
+    HRT_FLAG_NEE_EMITTERS = 1u << 7 /* with HRT_FLAG_NEE (alone: HRT_ERR_INVALID); may be combined with HRT_FLAG_NEE_ENV: sample the emitter
+                                    table instead of the light table.  It holds every DiffuseLight rect, box face and mesh
+                                    triangle, under any wrapper chain, and the unwrapped spheres (built at hrt_scene_create, see
+                                    hrt_emitter_table_build); the light is chosen by an alias table and a planar one sampled uniformly
+                                    over its world-space area.  A bounce that hits any entry gets the matching MIS weight; wrapped spheres
+                                    and free `triangle` prims (whose hit test does not accept their geometric triangle) still emit with
+                                    weight 1.  A scene without entries renders exactly as without the flag.  Shadow rays
+                                    count in hrt_stats::shadow_rays.  Megakernel: HRT_ERR_UNSUPPORTED. */
 };
 
 typedef struct hrt_rect { int32_t x0, y0, w, h; } hrt_rect;   /* y0 = row index from the TOP (pIdx / W) */
@@ -449,6 +457,15 @@ hrt_status hrt_math_probe(int device, int32_t op, int64_t n, const float* in, co
  * starts at exactly 0, ends at exactly 1 and is monotone; a row of weight 0 is all 0 but its last entry.  When the map has no table
  * (total weight 0 or not finite) every entry of both outputs is 0, so marginal_out[H] == 0 says "no table". */
 hrt_status hrt_env_table_build(const float* texels, int32_t W, int32_t H, int32_t channels, float* marginal_out, float* conditional_out);
+
+/* HRT_FLAG_NEE_EMITTERS' emitter table of a flattened scene (csrc/hrt_emitters.h), exactly as hrt_scene_create builds it;
+ * host only, no device needed.  Size query: every output NULL, *n_entries gets the number of entries (0: the scene has no table).  Fill:
+ * *n_entries = that number, and records_out gets 16 floats per entry (4 float4: prim bits, kind bits, P_sel, sub bits / origin or centre,
+ * area or radius / edge 1, wrapped / edge 2), shade_out 4 per entry (unit normal, P_sel / area; sphere: centre, -radius), thresh_out and
+ * alias_out one per alias slot, base_out one per prim (its first entry, -1: none).  P_sel is the probability the fp32 alias table
+ * realises. */
+hrt_status hrt_emitter_table_build(const hrt_flat_scene* flat, int64_t* n_entries, float* records_out, float* shade_out, float* thresh_out,
+                                   int32_t* alias_out, int32_t* base_out);
 
 /* Debug entry: a library built with -DHRT_DEBUG_BOUNDS checks every table index a hit record is built from (triangle of a mesh,
  * prim, material, texture, mesh, frontFace source) against its table, counts the violations per kind and carries on with index 0
