@@ -34,6 +34,7 @@ Q1_ROTQ_NORMALIZE, Q2_TRI_NO_TMIN, Q3_TRI_NO_FACE, Q4_SHEAR_FROM_ORIGIN = 1, 2, 
 QUIRKS_REFERENCE, QUIRKS_FIXED = 0xF, 0x0
 FLAG_STATS, FLAG_MEGAKERNEL, FLAG_TIMING, FLAG_THIN_LENS, FLAG_PROGRESS, FLAG_NEE, FLAG_NEE_ENV = 1, 2, 4, 8, 16, 32, 64
 FLAG_NEE_EMITTERS = 128
+FLAG_NEE_LOBES = 256
 
 
 # ---------------------------------------------------------------- structs (hrt.h)
@@ -241,11 +242,12 @@ def _ptr(a, t=_fp):
 
 # ---------------------------------------------------------------- host side
 def default_params(width, height, samples, quirks=QUIRKS_REFERENCE, seed=0, max_depth=50, stats=False, megakernel=False, timing=False,
-                   thin_lens=False, progress=False, nee=False, nee_env=False, nee_emitters=False):
+                   thin_lens=False, progress=False, nee=False, nee_env=False, nee_emitters=False, nee_lobes=False):
     """nee: next-event estimation with MIS for the scene's rect and sphere lights (FLAG_NEE).
     nee_env: also importance-sample the environment map (FLAG_NEE_ENV); implies nee.
     nee_emitters: sample every rect, box and mesh emitter, wrapped or not, by an alias table (FLAG_NEE_EMITTERS, DESIGN.md 4.7);
-    implies nee."""
+    implies nee.
+    nee_lobes: rough metal and medium vertices sample lights too (FLAG_NEE_LOBES); implies nee."""
     p = Params()
     _host.hrt_default_params(C.byref(p), width, height, samples)
     p.quirks = quirks
@@ -253,8 +255,8 @@ def default_params(width, height, samples, quirks=QUIRKS_REFERENCE, seed=0, max_
     p.seed_hi = (seed >> 32) & 0xFFFFFFFF
     p.max_depth = max_depth
     p.flags = (FLAG_STATS if stats else 0) | (FLAG_MEGAKERNEL if megakernel else 0) | (FLAG_TIMING if timing else 0) | \
-              (FLAG_THIN_LENS if thin_lens else 0) | (FLAG_PROGRESS if progress else 0) | (FLAG_NEE if nee or nee_env or nee_emitters else 0) | \
-              (FLAG_NEE_ENV if nee_env else 0) | (FLAG_NEE_EMITTERS if nee_emitters else 0)
+              (FLAG_THIN_LENS if thin_lens else 0) | (FLAG_PROGRESS if progress else 0) | (FLAG_NEE if nee or nee_env or nee_emitters or nee_lobes else 0) | \
+              (FLAG_NEE_ENV if nee_env else 0) | (FLAG_NEE_EMITTERS if nee_emitters else 0) | (FLAG_NEE_LOBES if nee_lobes else 0)
     return p
 
 

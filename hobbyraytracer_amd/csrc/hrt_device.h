@@ -1166,8 +1166,21 @@ __device__ inline float matscalar_value(const DScene& sc, const hrt_matscalar& m
 // Returns false when the path ends (DiffuseLight, absorbed Metal).
 // `lambert` (HRT_FLAG_NEE only; NULL otherwise): set to whether the scatter was Lambertian (a Lambertian, or a PBR whose mix
 // chose diffuse) -- the vertices that sample a light.
+// `lobe` (HRT_FLAG_NEE_LOBES only, material_scatter<true>; NULL otherwise): the other scatters that have a density -- a Metal (or a PBR
+// whose mix chose metal) of roughness >= HRT_NEE_RHO_MIN that the ray met from the side its normal faces: sd = c + rho sphericalRand(1), accepted when dot(sd, nn) > 0; an
+// Isotropic: sd = ballRand(1).  kind stays HRT_LOBE_NONE for everything else.
+#define HRT_LOBE_NONE 0
+#define HRT_LOBE_METAL 1
+#define HRT_LOBE_MEDIUM 2
+// The smallest roughness whose lobe is sampled as a light's: below it the lobe's cone (half-angle asin(rho)) is so narrow that
+// fp32 directions no longer resolve the density's edge (DESIGN.md 4.8 records the integral measured at this value).
+#define HRT_NEE_RHO_MIN 0.015625f
+struct NeeLobe { int kind; float rho; vec3 c, nn; };
+// (LOBE is a template parameter, not a test of the pointer: material_scatter<false> is then, statement for statement, the function it
+// was before the lobes, and the kernels of the other flags keep their registers.)
+template <bool LOBE = false>
 __device__ inline bool material_scatter(const DScene& sc, const DRec& rec, vec3 rin_d, const rng_ctx& ctx, vec3& emitted,
-                                        vec3& attenuation, vec3& so, vec3& sd, bool* lambert = nullptr) {
+                                        vec3& attenuation, vec3& so, vec3& sd, bool* lambert = nullptr, NeeLobe* lobe = nullptr) {
     int mat_i = rec.mat;
     HRT_BOUNDS(2, mat_i, sc.n_mats);
     const hrt_material& m = sc.lmats[mat_i];
@@ -1181,6 +1194,7 @@ __device__ inline bool material_scatter(const DScene& sc, const DRec& rec, vec3 
     if (kind == HRT_MAT_ISOTROPIC) {  // material.h:79-85
         sd = ball_rand(ctx);
         attenuation = matvec3_value(sc, m.albedo, rec.u, rec.v, rec.p);
+        if (LOBE) lobe->kind = HRT_LOBE_MEDIUM;
         return true;
     }
     const u32x4 dr = rng_draw(ctx, RNG_SCATTER, 0);
@@ -1204,6 +1218,9 @@ __device__ inline bool material_scatter(const DScene& sc, const DRec& rec, vec3 
         roughness = roughness < 1 ? roughness : 1;
         sd = reflected + roughness * sph + vec3(1.1920928955078125e-7f);
         attenuation = matvec3_value(sc, m.albedo, rec.u, rec.v, rec.p);
+        if (LOBE && roughness >= HRT_NEE_RHO_MIN && dot(reflected, nn) >= 0.0f) {   // (hit from behind its normal, Q-3: not eligible)
+            lobe->kind = HRT_LOBE_METAL; lobe->rho = roughness; lobe->c = reflected + vec3(1.1920928955078125e-7f); lobe->nn = nn;
+        }
         return dot(sd, nn) > 0;
     }
     // HRT_MAT_DIELECTRIC: material.h:204-229, 236-241
@@ -1257,6 +1274,53 @@ __device__ inline float nee_bsdf_pdf(vec3 n, vec3 w, float& t0, float& t1) {
 __device__ inline float nee_pick_root(float t0, float t1, uint32_t u) {
     const float a = t0 * t0, b = t1 * t1;
     return u01(u) * (a + b) < a ? t0 : t1;
+}
+// HRT_FLAG_NEE_LOBES: the density of normalize(sd) for sd = c + rho sphericalRand(1), as nee_bsdf_pdf of
+// m = c / rho (|m| = 1 / rho >= 1 for a Metal: the directions fill the cone of half-angle asin(rho) around c).  There
+// c^2 + 1 - r^2 cancels (r^2 ~ c^2 ~ 1 / rho^2), so D = 1 - |m x w|^2 instead (|w| = 1: r^2 - c^2 = |m x w|^2), which loses
+// nothing away from the cone's edge D = 0.  t0 / t1 = the positive roots of |t w - m| = 1; sd's own lengths are rho t_k.
+__device__ inline float nee_lobe_pdf(vec3 m, vec3 w, float& t0, float& t1) {
+    const float c = dot(w, m);
+    const vec3 x = cross(m, w);
+    const float D = 1.0f - dot(x, x);
+    t0 = 0.0f; t1 = 0.0f;
+    if (!(D > 0.0f) || !(D < 3.0e38f)) return 0.0f;
+    const float sD = sqrtf(D);
+    const float big = c >= 0.0f ? c + sD : c - sD;
+    const float other = (dot(m, m) - 1.0f) / big;
+    if (big > 0.0f) t0 = big;
+    if (other > 0.0f) t1 = other;
+    return (t0 * t0 + t1 * t1) / (4.0f * HRT_NEE_PI * sD);
+}
+// What a vertex keeps for its light sample: N = (m, p_b of the direction it scattered into), M = (nn, code) with
+//   code = 0: a Lambertian vertex (m = rec.normal; nee_bsdf_pdf, length t_k: the HRT_FLAG_NEE estimator, bit for bit),
+//   code > 0: a Metal lobe of roughness rho = code (m = c / rho; accepted when dot(w, nn) > 0; length rho t_k),
+//   code < 0: an Isotropic vertex (p_b = 1 / (4 pi); length cbrt(u): |ballRand(1)| has the density 3 r^2 on [0, 1]).
+// nee_vertex_pdf: p_b(w) times [accepted] and the roots; nee_vertex_len: the shadow ray's length for the root t_k and the word u
+// that chose it.  -DHRT_LOBES_TK_SHADOW (experiment only): the length t_k for every vertex.
+__device__ inline float nee_vertex_pdf(float4 N, float4 M, vec3 w, float& t0, float& t1) {
+    if (M.w == 0.0f) return nee_bsdf_pdf(vec3(N.x, N.y, N.z), w, t0, t1);
+    if (M.w < 0.0f) { t0 = 1.0f; t1 = 0.0f; return 1.0f / (4.0f * HRT_NEE_PI); }
+    t0 = 0.0f; t1 = 0.0f;
+    if (!(dot(w, vec3(M.x, M.y, M.z)) > 0.0f)) return 0.0f;
+    return nee_lobe_pdf(vec3(N.x, N.y, N.z), w, t0, t1);
+}
+// A Metal vertex takes its light sample only when its own bounce survived (an absorbed bounce, dot(sd, nn) <= 0, ends the path and
+// leaves no vertex).  The two draws are independent, so the sample is taken with the probability P_acc that sd lies above the
+// surface -- the share of the unit sphere around m above the plane through the origin with normal nn, (1 + m . nn) / 2 (a cap's
+// area is linear in its height) -- and its term is divided by it.  1 for the other vertices, which always survive.
+__device__ inline float nee_vertex_inv_acc(float4 N, float4 M) {
+    if (!(M.w > 0.0f)) return 1.0f;
+    const float h = 0.5f * (1.0f + dot(vec3(N.x, N.y, N.z), vec3(M.x, M.y, M.z)));
+    return h < 1.0f ? 1.0f / h : 1.0f;       // (h > 0: the vertex's own sd lay above the surface)
+}
+__device__ inline float nee_vertex_len(float code, float tk, uint32_t u) {
+#ifdef HRT_LOBES_TK_SHADOW
+    return tk;
+#else
+    if (code == 0.0f) return tk;
+    return code > 0.0f ? code * tk : cbrtf(u01(u));
+#endif
 }
 // The power heuristic's two weights, for densities a, b >= 0, written so that no inf * 0 or 0 / 0 can appear:
 //   nee_mis_bsdf(pb, q)   = pb^2 / (pb^2 + q^2)   (a bounce from an eligible vertex that hits a table light)

@@ -16,6 +16,7 @@
 //   k_wf_shade<STATS, true> / k_wf_shadow<false>   next-event estimation with MIS, HRT_FLAG_NEE.
 //   k_wf_shade<STATS, true, true> / k_wf_shadow<true> / k_env_rows / k_env_marginal   environment-map sampling, HRT_FLAG_NEE_ENV (4.6).
 //   k_wf_shade<STATS, true, ENV, true> / k_wf_shadow<ENV, true>   the emitter table, HRT_FLAG_NEE_EMITTERS (4.7).
+//   k_wf_shade<STATS, true, ENV, EMIT, true> / k_wf_shadow<ENV, EMIT, true>   light samples at rough metal and medium vertices, HRT_FLAG_NEE_LOBES (4.8).
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>   // types and prototypes only: the library is loaded on demand (rccl_api below)
 #include <dlfcn.h>
@@ -345,6 +346,10 @@ struct WfBuf {
     const int32_t* emit_base;    // per prim: its first entry, -1 if it has none (an entry = base + triangle index or box side)
     int n_emit;
 };
+// HRT_FLAG_NEE_LOBES (LOBES): N holds TWO float4 per position, the record above (its xyz then the lobe's m = c / rho) and
+// after it M = the vertex's acceptance normal nn.xyz and its lobe code (hrt_device.h nee_vertex_pdf: 0 Lambertian, rho > 0 Metal,
+// < 0 Isotropic).  (In N, not in arrays of its own: WfBuf is a kernel argument of every wavefront kernel, and must not grow.)
+#define HRT_NREC(pos) (LOBES ? (size_t)2 * (pos) : (size_t)(pos))
 // Task ownership.  Tasks differ in cost by orders of magnitude (a run of pixels under the mesh vs. a run of sky), so a
 // static wave -> task map leaves most waves idle while a few finish: plain striding (task = wave + i * n_waves) even
 // resonates with the film -- n_waves x T is a whole number of images for power-of-two films (8192 waves x 4096 slots =
@@ -1105,7 +1110,68 @@ __device__ HRT_WAVE_FN bool path_shade_nee(const DScene& sc, const hrt_params& p
     return ps.bounce >= pr.max_depth;
 }
 
-template <bool STATS, bool NEE = false, bool ENV = false, bool EMIT = false>
+// LOBES (HRT_FLAG_NEE_LOBES): a rough Metal scatter and an Isotropic one are eligible too; nrec = (m = c / rho, p_b) and
+// mrec = (nn, lobe code) describe the lobe for k_wf_shadow (hrt_device.h nee_vertex_pdf).
+// (A function of its own, not a parameter of path_shade_nee: the kernels of the other flags are then compiled from the statements they
+// always were, and keep their registers -- tests/test_nee_emitters_resources.py.  The weighting of `emitted` below is path_shade_nee's,
+// statement for statement: moving it into a helper both call gave k_wf_shade<true, true, true> 8 B of scratch
+// (tests/test_env_nee_resources.py), so a change to one of the two copies must be made to the other.)
+template <bool STATS, bool EMIT>
+__device__ HRT_WAVE_FN bool path_shade_lobes(const DScene& sc, const hrt_params& pr, const WfBuf& w, const rng_ctx& ctx, PathState& ps,
+                                           const WorldHit& wh, PathCounters& pc, float prev_pb, float4& nrec, float4& mrec) {
+    if (STATS && sc.lprims[wh.prim].kind == HRT_PRIM_MESH) pc.mesh_hits++;
+    DRec rec;
+    hit_record(sc, wh, ps.o, ps.d, pr.quirks, pr.t_min, rec);
+    vec3 emitted, attenuation, so, sd;
+    bool lambert = false;
+    NeeLobe lobe; lobe.kind = HRT_LOBE_NONE;
+    const bool b = material_scatter<true>(sc, rec, ps.d, ctx, emitted, attenuation, so, sd, &lambert, &lobe);
+    if (EMIT && !b && prev_pb >= 0.0f) {
+        int li = w.emit_base[wh.prim];
+        if (li >= 0) {
+            if (wh.sub >= 0) li += sub_tri(wh.sub);
+            const float4 S = w.emit_shade[li];
+            const vec3 wn = normalize(ps.d);
+            float q;
+            if (S.w >= 0.0f) q = emit_q_planar(S, ps.o, wn, rec.p);
+            else            // an unwrapped sphere (S = centre, -r): the HRT_FLAG_NEE density times its P_sel
+                q = w.emit_rec[HRT_EMIT_REC * li].z * emit_pdf_sphere(S, ps.o, wn, rec.p);
+            emitted = emitted * nee_mis_bsdf(prev_pb, q);
+        }
+    } else if (!b && prev_pb >= 0.0f) {
+        const int li = w.light_of[wh.prim];
+        if (li >= 0) {   // q from the ray's origin to the hit: the density the light strategy gives this direction
+            const float4 L0 = w.lights[HRT_NEE_REC * li], L1 = w.lights[HRT_NEE_REC * li + 1], L2 = w.lights[HRT_NEE_REC * li + 2];
+            const float q = L0.z * nee_pdf(L0, L1, L2, ps.o, normalize(ps.d), rec.p);
+            emitted = emitted * nee_mis_bsdf(prev_pb, q);
+        }
+    }
+    ps.result += ps.atten * emitted;
+    if (!b) return true;
+    ps.atten *= attenuation;
+    ps.o = so; ps.d = sd;
+    ps.bounce++;
+    nrec = make_float4(rec.normal.x, rec.normal.y, rec.normal.z, -1.0f);
+    if (lambert) {
+        float t0, t1;
+        const float pb = nee_bsdf_pdf(rec.normal, normalize(sd), t0, t1);
+        if (pb > 0.0f) nrec.w = pb;
+    }
+    mrec = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (lobe.kind == HRT_LOBE_METAL) {
+        const vec3 m = lobe.c / lobe.rho;
+        float t0, t1;
+        const float pb = nee_lobe_pdf(m, normalize(sd), t0, t1);
+        nrec = make_float4(m.x, m.y, m.z, pb > 0.0f ? pb : -1.0f);
+        mrec = make_float4(lobe.nn.x, lobe.nn.y, lobe.nn.z, lobe.rho);
+    } else if (lobe.kind == HRT_LOBE_MEDIUM) {
+        nrec.w = 1.0f / (4.0f * HRT_NEE_PI);
+        mrec.w = -1.0f;
+    }
+    return ps.bounce >= pr.max_depth;
+}
+
+template <bool STATS, bool NEE = false, bool ENV = false, bool EMIT = false, bool LOBES = false>
 __device__ HRT_WAVE_FN void wf_shade_task(const DScene& sc, const hrt_params& pr, const RenderMap& map, const WfScene& ws, unsigned n_local, int s0, int round,
                                      const WfBuf& w, unsigned task, unsigned n, unsigned lane, unsigned long long lt, MissQueue& mq,
                                      PathCounters& pc, unsigned& n_seg, unsigned& n_culled, unsigned& live_out, unsigned& qn_out, unsigned& rn_out) {
@@ -1125,7 +1191,8 @@ __device__ HRT_WAVE_FN void wf_shade_task(const DScene& sc, const hrt_params& pr
         bool missed = false;
         WorldHit wh; wh.prim = -1; wh.sub = -1; wh.t = 0.0f; wh.s_prim = -1; wh.s_sub = -1; wh.s_t = 0.0f;
         float prev_pb = -1.0f;       // ENV: the previous vertex's p_b (the miss queue needs it too)
-        if (ENV && round > 0 && j0 + lane < n) prev_pb = w.N[par][pos].w;
+        if (LOBES) { if (ENV && round > 0 && j0 + lane < n) prev_pb = w.N[par][HRT_NREC(pos)].w; }
+        else if (ENV && round > 0 && j0 + lane < n) prev_pb = w.N[par][pos].w;
         if (j0 + lane < n) {
             n_seg++;
             ps.o = vec3(a.x, a.y, a.z); ps.d = vec3(a.w, b.x, b.y);
@@ -1155,9 +1222,12 @@ __device__ HRT_WAVE_FN void wf_shade_task(const DScene& sc, const hrt_params& pr
         }
         HRT_SP_MARK(1);
         float4 nrec = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+        float4 mrec;                 // LOBES only
+        if (LOBES) mrec = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         if (j0 + lane < n && !missed) {
             bool ended;
-            if (ENV) ended = path_shade_nee<STATS, EMIT>(sc, pr, w, ctx, ps, wh, pc, prev_pb, nrec);
+            if (LOBES) ended = path_shade_lobes<STATS, EMIT>(sc, pr, w, ctx, ps, wh, pc, ENV ? prev_pb : (round > 0 ? w.N[par][HRT_NREC(pos)].w : -1.0f), nrec, mrec);
+            else if (ENV) ended = path_shade_nee<STATS, EMIT>(sc, pr, w, ctx, ps, wh, pc, prev_pb, nrec);
             else if (EMIT) ended = path_shade_nee<STATS, true>(sc, pr, w, ctx, ps, wh, pc, round > 0 ? w.N[par][pos].w : -1.0f, nrec);
             else if (NEE) ended = path_shade_nee<STATS>(sc, pr, w, ctx, ps, wh, pc, round > 0 ? w.N[par][pos].w : -1.0f, nrec);
             else ended = path_shade<STATS>(sc, pr, ctx, ps, wh, pc);
@@ -1184,7 +1254,8 @@ __device__ HRT_WAVE_FN void wf_shade_task(const DScene& sc, const hrt_params& pr
             ctx.bounce = (uint32_t)(round + 1);   // the next segment's draws (ConstantMedium::hit inside wf_prepare)
             enq = wf_prepare<STATS>(sc, pr, 0, ws.first_mesh, ws.has_mesh ? ws.first_mesh : -1, ps.o, ps.d, ctx, closest, prim, sub, mr, n_culled);
             wf_store_state(w, nxt, npos, ps, closest, slot, prim, sub);
-            if (NEE) w.N[nxt][npos] = nrec;
+            if (LOBES) { w.N[nxt][HRT_NREC(npos)] = nrec; w.N[nxt][HRT_NREC(npos) + 1] = mrec; }
+            else if (NEE) w.N[nxt][npos] = nrec;
         }
         HRT_SP_MARK(3);
         out += (unsigned)__popcll(ma);
@@ -1214,7 +1285,8 @@ __device__ HRT_WAVE_FN void wf_shade_counters(const WfBuf& w, DeviceCounters* co
 #endif
 // ENV (HRT_FLAG_NEE_ENV, with NEE only): the environment map's MIS weight on escapes from eligible vertices
 // EMIT (HRT_FLAG_NEE_EMITTERS, with NEE only): the MIS weight of emission found on any entry of the emitter table
-template <bool STATS, bool NEE, bool ENV = false, bool EMIT = false>
+// LOBES (HRT_FLAG_NEE_LOBES, with NEE only): rough Metal and Isotropic vertices are eligible too
+template <bool STATS, bool NEE, bool ENV = false, bool EMIT = false, bool LOBES = false>
 __global__ __launch_bounds__(256, HRT_SHADE_WAVES) void k_wf_shade(DScene sc, hrt_params pr, RenderMap map, WfScene ws, unsigned n_local, int s0, int round,
                                                   WfBuf w, DeviceCounters* counters) {
     const unsigned lane = threadIdx.x & 63u;
@@ -1232,7 +1304,7 @@ __global__ __launch_bounds__(256, HRT_SHADE_WAVES) void k_wf_shade(DScene sc, hr
     PathCounters pc; pc.rays = 0; pc.samples = 0; pc.mesh_hits = 0; pc.env_lookups = 0; pc.bvh.box_tests = 0; pc.bvh.tri_tests = 0;
     HRT_FOR_MY_TASKS(task, w, wave, lane) {
         unsigned live, qn, rn;
-        wf_shade_task<STATS, NEE, ENV, EMIT>(sc, pr, map, ws, n_local, s0, round, w, task, HRT_UNIFORM(w.live[task]), lane, lt, mq, pc, n_seg, n_culled, live, qn, rn);
+        wf_shade_task<STATS, NEE, ENV, EMIT, LOBES>(sc, pr, map, ws, n_local, s0, round, w, task, HRT_UNIFORM(w.live[task]), lane, lt, mq, pc, n_seg, n_culled, live, qn, rn);
         if (lane == 0) { w.live[task] = live; w.qn[task] = qn; w.rn[task] = rn; if (rn) wf_ref_publish(w, task, rn); }
     }
     if (mq.count) missq_flush<STATS, ENV>(sc, w, mq, lane, mq.count, pc);
@@ -1245,7 +1317,8 @@ __global__ __launch_bounds__(256, HRT_SHADE_WAVES) void k_wf_shade(DScene sc, hr
 // light; it sees the light exactly when the closest hit IS the sampled light's prim.  Its ConstantMedium draws use the bounce field
 // round | HRT_RNG_SHADOW.  The term atten Le pb q / (pb^2 + q^2) is added to the slot's `direct` sum.
 // The eligible positions are compacted per wave first (ballots into an LDS queue, as the miss queue of k_wf_shade does), so that the
-// world_hit of 64 shadow rays runs with full lanes whatever fraction of the survivors is eligible (metal, glass and media are not).
+// world_hit of 64 shadow rays runs with full lanes whatever fraction of the survivors is eligible (glass never is; rough metal and
+// media only with LOBES).
 // -DHRT_NEE_UNIT_SHADOW (experiment only): cast the shadow ray with the unit direction w instead of t_k w -- the biased
 // estimator the design avoids, kept compilable so the unbiasedness test can be shown to catch it.
 // ENV (HRT_FLAG_NEE_ENV): after the table-light sample (if the scene has table lights), the same vertex takes one
@@ -1258,8 +1331,14 @@ __global__ __launch_bounds__(256, HRT_SHADE_WAVES) void k_wf_shade(DScene sc, hr
 // entry's triangle or side.  t_max: reach / t_k x 1.001 for an unwrapped entry; inf under a wrapper, whose child measures t in its own
 // units (quirk Q-1).  -DHRT_EMIT_EUCLID_TMAX (experiment only): the Euclidean cut for wrapped entries too -- kept
 // compilable so the unbiasedness test can be shown to catch it.
+// LOBES (HRT_FLAG_NEE_LOBES): the vertex's density, acceptance and length law come from its lobe (N, M: hrt_device.h
+// nee_vertex_pdf / nee_vertex_len) in all three samplers: d = rho t_k w at a Metal vertex, cbrt(u) w at an Isotropic one (u = the word
+// that chooses the root elsewhere), whose shadow ray starts inside the medium -- world_hit's own keyed free-path draw is its
+// transmittance estimate.  A Metal vertex exists only when its bounce was not absorbed, so its terms are divided by that probability
+// (nee_vertex_inv_acc).  -DHRT_LOBES_NO_ACC (experiment only): without that division, kept compilable so the tests can be
+// shown to catch it.
 #define HRT_SHADOWQ_CAP 128
-template <bool ENV, bool EMIT = false>
+template <bool ENV, bool EMIT = false, bool LOBES = false>
 __global__ __launch_bounds__(HRT_BLOCK) void k_wf_shadow(DScene sc, hrt_params pr, RenderMap map, unsigned n_local, int s0, int round, WfBuf w) {
     __shared__ int s_stack[HRT_STACK_DEPTH * HRT_BLOCK];
     __shared__ __attribute__((aligned(16))) uint32_t s_tables[HRT_TABLE_LDS_BYTES / 4];
@@ -1286,7 +1365,7 @@ __global__ __launch_bounds__(HRT_BLOCK) void k_wf_shadow(DScene sc, hrt_params p
                 continue;
             }
             const unsigned pos = task * w.T + j0 + lane;
-            const bool elig = j0 + lane < n && w.N[nxt][pos].w >= 0.0f;
+            const bool elig = j0 + lane < n && w.N[nxt][HRT_NREC(pos)].w >= 0.0f;
             const unsigned long long m = __ballot(elig);
             if (elig) q[qn + lanes_below(m)] = pos;
             qn += (unsigned)__popcll(m);          // < 64 + 64 <= HRT_SHADOWQ_CAP
@@ -1299,7 +1378,13 @@ __global__ __launch_bounds__(HRT_BLOCK) void k_wf_shadow(DScene sc, hrt_params p
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         qn -= k;
         if (lane >= k) continue;
-        const float4 nr = w.N[nxt][pos];
+        const float4 nr = w.N[nxt][HRT_NREC(pos)];
+        const float4 mr = LOBES ? w.N[nxt][HRT_NREC(pos) + 1] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+#ifdef HRT_LOBES_NO_ACC   // experiment only: no correction for the bounce's survival -- the biased estimator
+        const float inv_acc = 1.0f;
+#else
+        const float inv_acc = LOBES ? nee_vertex_inv_acc(nr, mr) : 1.0f;
+#endif     // a Metal vertex samples only when its bounce survived
         const float4 a = w.S0[nxt][pos], b = w.S1[nxt][pos];
         const float az = w.S3[nxt][pos];
         const unsigned slot = __float_as_uint(w.S2[nxt][pos].w);
@@ -1318,9 +1403,10 @@ __global__ __launch_bounds__(HRT_BLOCK) void k_wf_shadow(DScene sc, hrt_params p
                                                         : emit_sample_planar(kind == HRT_EMIT_TRI, E1, E2, w.emit_rec[HRT_EMIT_REC * li + 3], x, u.y, u.z, wd, pl, reach);
                 if (!ok) return;
                 float t0, t1;
-                const float pb = nee_bsdf_pdf(vec3(nr.x, nr.y, nr.z), wd, t0, t1);
+                const float pb = LOBES ? nee_vertex_pdf(nr, mr, wd, t0, t1) : nee_bsdf_pdf(vec3(nr.x, nr.y, nr.z), wd, t0, t1);
                 if (!(pb > 0.0f)) return;
-                const float tk = nee_pick_root(t0, t1, u.w);
+                const float tk = LOBES ? nee_vertex_len(mr.w, nee_pick_root(t0, t1, u.w), u.w) : nee_pick_root(t0, t1, u.w);
+                if (LOBES && !(tk > 0.0f)) return;
                 const vec3 d = tk * wd;
 #ifdef HRT_EMIT_EUCLID_TMAX
                 const float t_max = reach / tk * 1.001f;
@@ -1335,7 +1421,7 @@ __global__ __launch_bounds__(HRT_BLOCK) void k_wf_shadow(DScene sc, hrt_params p
                 if (wh.prim != __float_as_int(E0.x) || (esub >= 0 && sub_tri(wh.sub) != esub)) return;
                 DRec rec;
                 hit_record(sc, wh, x, d, pr.quirks, pr.t_min, rec);
-                const vec3 term = vec3(b.z, b.w, az) * nee_emitted(sc, rec) * nee_mis_shadow(pb, E0.z * pl);
+                const vec3 term = vec3(b.z, b.w, az) * nee_emitted(sc, rec) * (LOBES ? nee_mis_shadow(pb, E0.z * pl) * inv_acc : nee_mis_shadow(pb, E0.z * pl));
                 const float4 acc = w.direct[slot];
                 w.direct[slot] = make_float4(acc.x + term.x, acc.y + term.y, acc.z + term.z, 0.0f);
                 return;
@@ -1346,12 +1432,13 @@ __global__ __launch_bounds__(HRT_BLOCK) void k_wf_shadow(DScene sc, hrt_params p
             float pl, reach;
             if (!nee_sample(L0, L1, L2, x, u.y, u.z, wd, pl, reach)) return;
             float t0, t1;
-            const float pb = nee_bsdf_pdf(vec3(nr.x, nr.y, nr.z), wd, t0, t1);
+            const float pb = LOBES ? nee_vertex_pdf(nr, mr, wd, t0, t1) : nee_bsdf_pdf(vec3(nr.x, nr.y, nr.z), wd, t0, t1);
             if (!(pb > 0.0f)) return;
 #ifdef HRT_NEE_UNIT_SHADOW
             const float tk = 1.0f;
 #else
-            const float tk = nee_pick_root(t0, t1, u.w);
+            const float tk = LOBES ? nee_vertex_len(mr.w, nee_pick_root(t0, t1, u.w), u.w) : nee_pick_root(t0, t1, u.w);
+            if (LOBES && !(tk > 0.0f)) return;
 #endif
             const vec3 d = tk * wd;
             ctx.bounce = (uint32_t)round | HRT_RNG_SHADOW;
@@ -1361,7 +1448,7 @@ __global__ __launch_bounds__(HRT_BLOCK) void k_wf_shadow(DScene sc, hrt_params p
             if (wh.prim != __float_as_int(L0.x)) return;
             DRec rec;
             hit_record(sc, wh, x, d, pr.quirks, pr.t_min, rec);
-            const vec3 term = vec3(b.z, b.w, az) * nee_emitted(sc, rec) * nee_mis_shadow(pb, L0.z * pl);
+            const vec3 term = vec3(b.z, b.w, az) * nee_emitted(sc, rec) * (LOBES ? nee_mis_shadow(pb, L0.z * pl) * inv_acc : nee_mis_shadow(pb, L0.z * pl));
             const float4 acc = w.direct[slot];
             w.direct[slot] = make_float4(acc.x + term.x, acc.y + term.y, acc.z + term.z, 0.0f);
         }();
@@ -1371,9 +1458,12 @@ __global__ __launch_bounds__(HRT_BLOCK) void k_wf_shadow(DScene sc, hrt_params p
             float pe, t0, t1;
             int ci, cj;
             if (!env_sample(w.env_marg, w.env_cond, w.env_w, w.env_h, rng_draw(ctx, RNG_ENV, 0), we, pe, ci, cj)) continue;
-            const float pb = nee_bsdf_pdf(vec3(nr.x, nr.y, nr.z), we, t0, t1);
+            const float pb = LOBES ? nee_vertex_pdf(nr, mr, we, t0, t1) : nee_bsdf_pdf(vec3(nr.x, nr.y, nr.z), we, t0, t1);
             if (!(pb > 0.0f)) continue;
-            const vec3 d = nee_pick_root(t0, t1, rng_draw(ctx, RNG_ENV, 1).x) * we;
+            const uint32_t ur = rng_draw(ctx, RNG_ENV, 1).x;
+            const float te = LOBES ? nee_vertex_len(mr.w, nee_pick_root(t0, t1, ur), ur) : nee_pick_root(t0, t1, ur);
+            if (LOBES && !(te > 0.0f)) continue;
+            const vec3 d = te * we;
             pe = env_pdf(w.env_marg, w.env_cond, w.env_w, w.env_h, d);   // the density of the texel background_value reads for d
             if (!(pe > 0.0f)) continue;
             ctx.bounce = (uint32_t)round | HRT_RNG_SHADOW | HRT_RNG_SHADOW_ENV;
@@ -1381,7 +1471,7 @@ __global__ __launch_bounds__(HRT_BLOCK) void k_wf_shadow(DScene sc, hrt_params p
             DCounters cnt; cnt.box_tests = 0; cnt.tri_tests = 0;
             const WorldHit wh = world_hit<false>(sc, x, d, pr.t_min, __builtin_huge_valf(), pr.quirks, ctx, stack, cnt);
             if (wh.prim >= 0) continue;
-            const vec3 term = vec3(b.z, b.w, az) * background_value(sc, d) * nee_mis_shadow(pb, pe);
+            const vec3 term = vec3(b.z, b.w, az) * background_value(sc, d) * (LOBES ? nee_mis_shadow(pb, pe) * inv_acc : nee_mis_shadow(pb, pe));
             const float4 acc = w.direct[slot];
             w.direct[slot] = make_float4(acc.x + term.x, acc.y + term.y, acc.z + term.z, 0.0f);
         }
@@ -1787,6 +1877,7 @@ struct WfWorkspace {          // device workspace of the wavefront pipeline (gro
     size_t slots = 0;
     int depth = 0, n_mesh = 0;
     bool nee = false;            // holds the HRT_FLAG_NEE buffers (WfBuf::N, direct, wave_shadow)
+    bool lobes = false;          // WfBuf::N holds two float4 per position (HRT_FLAG_NEE_LOBES)
     WfBuf buf{};
 };
 
@@ -2034,6 +2125,7 @@ hrt_status check_params(const hrt_params* p) {
     if (!(p->t_min == p->t_min)) return fail(HRT_ERR_INVALID, "t_min is NaN");
     if ((p->flags & HRT_FLAG_NEE_ENV) && !(p->flags & HRT_FLAG_NEE)) return fail(HRT_ERR_INVALID, "HRT_FLAG_NEE_ENV needs HRT_FLAG_NEE");
     if ((p->flags & HRT_FLAG_NEE_EMITTERS) && !(p->flags & HRT_FLAG_NEE)) return fail(HRT_ERR_INVALID, "HRT_FLAG_NEE_EMITTERS needs HRT_FLAG_NEE");
+    if ((p->flags & HRT_FLAG_NEE_LOBES) && !(p->flags & HRT_FLAG_NEE)) return fail(HRT_ERR_INVALID, "HRT_FLAG_NEE_LOBES needs HRT_FLAG_NEE");
     if ((p->flags & HRT_FLAG_MEGAKERNEL) && (p->flags & HRT_FLAG_NEE)) return fail(HRT_ERR_UNSUPPORTED, "next-event estimation renders on the wavefront pipeline only");
     return HRT_OK;
 }
@@ -2101,14 +2193,14 @@ hrt_status launch_megakernel(hrt_scene* sc, const hrt_camera* cam, const hrt_par
 // whose paths die early (open scenes: C4 shiny_teapot spends 22 batches at a 48 Mi cap, 141 ms; 2 batches, 91 ms) want
 // the largest batch that fits: 184 B per slot, up to 60 % of the free HBM (288 GB per MI355X) and 2^31 slots.  The
 // workspace is only ever as large as the batch needs (the headline frame: 41 M slots = 7.5 GB).
-// (HRT_FLAG_NEE: 48 B more per slot, WfBuf::N and direct)
-size_t wf_max_slots(const hrt_scene* sc, bool nee = false) {
+// (HRT_FLAG_NEE: 48 B more per slot, WfBuf::N and direct; HRT_FLAG_NEE_LOBES: another 32, the second float4 of WfBuf::N)
+size_t wf_max_slots(const hrt_scene* sc, bool nee = false, bool lobes = false) {
     if (const char* e = getenv("HRT_WF_MAX_SLOTS")) { long long v = atoll(e); if (v > 0) return (size_t)v; }
     size_t cap = (size_t)48 << 20;
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
         free_b += sc->wf.bytes;                          // what we hold already can be re-used
-        cap = std::max(cap, (size_t)((double)free_b * 0.6 / (nee ? 232.0 : 184.0)));
+        cap = std::max(cap, (size_t)((double)free_b * 0.6 / (lobes ? 264.0 : (nee ? 232.0 : 184.0))));
     }
     return std::min(cap, (size_t)1 << 31);
 }
@@ -2119,10 +2211,10 @@ size_t wf_counter_words(int depth, int n_mesh) { return (size_t)256 * (2 + (size
 // ... and of 512 words per traversal launch for its ref-walk lists (WfBuf::ref_prod / ref_cons), + one block nobody reads
 size_t wf_ref_counter_words(int depth, int n_mesh) { return (size_t)512 * ((size_t)depth * (size_t)std::max(1, n_mesh) + 1); }
 
-hrt_status wf_reserve(hrt_scene* sc, size_t slots, int depth, bool nee) {
+hrt_status wf_reserve(hrt_scene* sc, size_t slots, int depth, bool nee, bool lobes) {
     WfWorkspace& w = sc->wf;
     const int n_mesh = (int)sc->mesh_prims.size();
-    if (w.base && w.slots >= slots && w.depth >= depth && w.n_mesh == n_mesh && (w.nee || !nee)) return HRT_OK;
+    if (w.base && w.slots >= slots && w.depth >= depth && w.n_mesh == n_mesh && (w.nee || !nee) && (w.lobes || !lobes)) return HRT_OK;
     if (w.base) { HIPCHK(hipDeviceSynchronize()); w = WfWorkspace(); }
     const size_t max_tasks = slots / 64 + 1;   // the smallest task HRT_WF_TASK_SIZE can ask for is 64 positions (the default is >= 256)
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
@@ -2132,7 +2224,8 @@ hrt_status wf_reserve(hrt_scene* sc, size_t slots, int depth, bool nee) {
     const size_t ref_cap = max_tasks / HRT_REF_GROUPS + 1;
     const size_t total = (sc->ds.stale_ff ? 12 : 11) * f4 + 2 * i4 + 3 * al(max_tasks * sizeof(unsigned)) + al(ctr_words * sizeof(unsigned)) + al(ref_cap * HRT_REF_GROUPS * sizeof(uint2)) +
                          al((size_t)sc->n_cus * 32 * sizeof(unsigned long long)) +                                     // 184 B per slot
-                         (nee ? 3 * f4 + al((size_t)sc->n_cus * 32 * sizeof(unsigned long long)) : 0);                 // + 48 with NEE
+                         (nee ? 3 * f4 + al((size_t)sc->n_cus * 32 * sizeof(unsigned long long)) : 0) +                // + 48 with NEE
+                         (lobes ? 2 * f4 : 0);                                                                         // + 32 with NEE_LOBES
     DevBuf base;
     HRTCHK(base.alloc(total, "hipMalloc(wavefront workspace)"));
     char* p = base.get<char>();
@@ -2153,11 +2246,11 @@ hrt_status wf_reserve(hrt_scene* sc, size_t slots, int depth, bool nee) {
     w.buf.wave_rays = (unsigned long long*)take(al((size_t)w.buf.n_wave_rays * sizeof(unsigned long long)));
     HIPCHK(hipMemset(w.buf.wave_rays, 0, (size_t)w.buf.n_wave_rays * sizeof(unsigned long long)));
     if (nee) {
-        w.buf.N[0] = (float4*)take(f4); w.buf.N[1] = (float4*)take(f4); w.buf.direct = (float4*)take(f4);
+        w.buf.N[0] = (float4*)take((lobes ? 2 : 1) * f4); w.buf.N[1] = (float4*)take((lobes ? 2 : 1) * f4); w.buf.direct = (float4*)take(f4);
         w.buf.wave_shadow = (unsigned long long*)take(al((size_t)w.buf.n_wave_rays * sizeof(unsigned long long)));
         HIPCHK(hipMemset(w.buf.wave_shadow, 0, (size_t)w.buf.n_wave_rays * sizeof(unsigned long long)));
     }
-    w.base = std::move(base); w.bytes = total; w.slots = slots; w.depth = depth; w.n_mesh = n_mesh; w.nee = nee;
+    w.base = std::move(base); w.bytes = total; w.slots = slots; w.depth = depth; w.n_mesh = n_mesh; w.nee = nee; w.lobes = lobes;
     return HRT_OK;
 }
 
@@ -2177,7 +2270,9 @@ hrt_status launch_wavefront(hrt_scene* sc, const hrt_camera* cam, const hrt_para
     // no table light either (the emitter table holds every one), so it renders as HRT_FLAG_NEE (or HRT_FLAG_NEE_ENV) would.
     const bool emit = (pr->flags & HRT_FLAG_NEE) != 0 && (pr->flags & HRT_FLAG_NEE_EMITTERS) != 0 && sc->n_emit > 0;
     const bool nee = (pr->flags & HRT_FLAG_NEE) != 0 && (sc->n_lights > 0 || env || emit);
-    size_t cap = wf_max_slots(sc, nee);
+    // HRT_FLAG_NEE_LOBES widens which vertices sample whatever the flags above sample: nothing to sample, nothing to widen.
+    const bool lobes = nee && (pr->flags & HRT_FLAG_NEE_LOBES) != 0;
+    size_t cap = wf_max_slots(sc, nee, lobes);
     const int s_end = s_first + s_count;
     int chunk = (int)std::min<size_t>((size_t)s_count, std::max<size_t>(1, cap / n_local));
     // (the largest batches that fit plus a remainder, NOT equal batches: C4 on one GPU takes 92.8 ms as 453 + 59 samples and
@@ -2186,7 +2281,7 @@ hrt_status launch_wavefront(hrt_scene* sc, const hrt_camera* cam, const hrt_para
     for (;;) {   // the memory estimate can be stale (other processes on the device): halve the batch on OOM
         const size_t slots = (size_t)n_local * chunk;
         if (slots >= ((size_t)1 << 32) - 4096) return fail(HRT_ERR_UNSUPPORTED, "tile too large for 32-bit slot ids");
-        st = wf_reserve(sc, slots, D, nee);
+        st = wf_reserve(sc, slots, D, nee, lobes);
         if (st != HRT_ERR_OOM || chunk == 1) break;
         chunk = (chunk + 1) / 2;
     }
@@ -2321,7 +2416,12 @@ hrt_status launch_wavefront(hrt_scene* sc, const hrt_camera* cam, const hrt_para
             }
             next_counters((unsigned)task_blocks * 4u);
             w.ref_prod = ref_block(r + 1, 0); w.ref_cons = ref_block(D, 0);
-            if (emit) {
+            if (lobes) {
+                with_bool(env, [&](auto E) { with_bool(emit, [&](auto M) { with_bool(stats, [&](auto S) {
+                    hipLaunchKernelGGL((k_wf_shade<decltype(S)::value, true, decltype(E)::value, decltype(M)::value, true>), dim3(task_blocks), dim3(256), 0, stream, sc->ds, *pr,
+                                       map, ws, n_local, s0, r, w, sc->d_counters);
+                }); }); });
+            } else if (emit) {
                 with_bool(env, [&](auto E) { with_bool(stats, [&](auto S) {
                     hipLaunchKernelGGL((k_wf_shade<decltype(S)::value, true, decltype(E)::value, true>), dim3(task_blocks), dim3(256), 0, stream, sc->ds, *pr, map, ws,
                                        n_local, s0, r, w, sc->d_counters);
@@ -2340,7 +2440,11 @@ hrt_status launch_wavefront(hrt_scene* sc, const hrt_camera* cam, const hrt_para
             if (nee && r + 1 < D) {   // survivors of the last round: none (bounce + 1 < max_depth)
                 // (launches per round with NEE: pre + ext per mesh, stale, shade, shadow <= the 2 * max(1, n_mesh) + 2 of wf_counter_words)
                 next_counters((unsigned)task_blocks * 4u);
-                if (emit)
+                if (lobes)
+                    with_bool(env, [&](auto E) { with_bool(emit, [&](auto M) {
+                        hipLaunchKernelGGL((k_wf_shadow<decltype(E)::value, decltype(M)::value, true>), dim3(task_blocks), dim3(HRT_BLOCK), 0, stream, sc->ds, *pr, map, n_local, s0, r, w);
+                    }); });
+                else if (emit)
                     hipLaunchKernelGGL((env ? k_wf_shadow<true, true> : k_wf_shadow<false, true>), dim3(task_blocks), dim3(HRT_BLOCK), 0, stream, sc->ds, *pr, map, n_local, s0, r, w);
                 else
                     hipLaunchKernelGGL(env ? k_wf_shadow<true> : k_wf_shadow<false>, dim3(task_blocks), dim3(HRT_BLOCK), 0, stream, sc->ds, *pr, map, n_local, s0, r, w);

@@ -15,6 +15,7 @@
 //     --nee (next-event estimation with MIS for the scene's rect and sphere lights; off = the reference's estimator)
 //     --nee-env (--nee and environment-map importance sampling; implies --nee)
 //     --nee-emitters (--nee over every rect, box and mesh emitter, wrapped or not; implies --nee)
+//     --nee-lobes (--nee at rough metal and medium vertices too; implies --nee)
 //     --no-progress (no reporter thread and no progress counter on the device: main.cpp:97-109), --progress-ms N (its interval, 500)
 //     --rccl (gather the film through an RCCL communicator even on one GPU; with --gpus N > 1 it always is)
 //     --adaptive T (adaptive sampling: a pixel stops once the relative standard error of its mean luminance is below T;
@@ -84,6 +85,7 @@ int main(int argc, char** argv) {
         else if (a == "--nee") opt.nee = true;
         else if (a == "--nee-env") { opt.nee = true; opt.nee_env = true; }
         else if (a == "--nee-emitters") { opt.nee = true; opt.nee_emitters = true; }
+        else if (a == "--nee-lobes") { opt.nee = true; opt.nee_lobes = true; }
         else if (a == "--obj-indices") { std::string v = next("--obj-indices"); setenv("HRT_OBJ_INDICES", v == "rebased" ? "rebased" : "reference", 1); }
         else if (a == "--bvh") {     // who builds the meshes' culling trees: the host (binned SAH, default) or the GPU (gpu-sah: the same tree; lbvh: fastest to build, +16 % box tests)
             const std::string v = next("--bvh");

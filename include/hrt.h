@@ -249,7 +249,7 @@ enum {
                                     the sky when it hits nothing; an escaping bounce from such a vertex gets the matching MIS weight.
                                     Both shadow rays count in hrt_stats::shadow_rays.  A background without a table (not an environment
                                     map, or one of total weight 0) renders exactly as HRT_FLAG_NEE alone.  Megakernel: HRT_ERR_UNSUPPORTED. */
-    HRT_FLAG_NEE_EMITTERS = 1u << 7 /* with HRT_FLAG_NEE (alone: HRT_ERR_INVALID); may be combined with HRT_FLAG_NEE_ENV: sample the emitter
+    HRT_FLAG_NEE_EMITTERS = 1u << 7, /* with HRT_FLAG_NEE (alone: HRT_ERR_INVALID); may be combined with HRT_FLAG_NEE_ENV: sample the emitter
                                     table instead of the light table.  It holds every DiffuseLight rect, box face and mesh
                                     triangle, under any wrapper chain, and the unwrapped spheres (built at hrt_scene_create, see
                                     hrt_emitter_table_build); the light is chosen by an alias table and a planar one sampled uniformly
@@ -257,6 +257,12 @@ enum {
                                     and free `triangle` prims (whose hit test does not accept their geometric triangle) still emit with
                                     weight 1.  A scene without entries renders exactly as without the flag.  Shadow rays
                                     count in hrt_stats::shadow_rays.  Megakernel: HRT_ERR_UNSUPPORTED. */
+    HRT_FLAG_NEE_LOBES = 1u << 8 /* with HRT_FLAG_NEE (alone: HRT_ERR_INVALID); may be combined with HRT_FLAG_NEE_ENV and HRT_FLAG_NEE_EMITTERS:
+                                    the vertices that sample a light are, besides the Lambertian ones, every Metal scatter (a Metal, or a
+                                    PBR whose mix chose metal) of roughness >= 1/64 and every Isotropic one (a ConstantMedium hit)
+                                    (DESIGN.md 4.8); a bounce from such a vertex gets the matching MIS weight.  Dielectric and UVTest
+                                    scatters and smoother metals keep weight 1.  Where the other NEE flags have nothing to sample the flag
+                                    changes nothing.  Megakernel: HRT_ERR_UNSUPPORTED. */
 };
 
 typedef struct hrt_rect { int32_t x0, y0, w, h; } hrt_rect;   /* y0 = row index from the TOP (pIdx / W) */
