@@ -35,6 +35,7 @@ QUIRKS_REFERENCE, QUIRKS_FIXED = 0xF, 0x0
 FLAG_STATS, FLAG_MEGAKERNEL, FLAG_TIMING, FLAG_THIN_LENS, FLAG_PROGRESS, FLAG_NEE, FLAG_NEE_ENV = 1, 2, 4, 8, 16, 32, 64
 FLAG_NEE_EMITTERS = 128
 FLAG_NEE_LOBES = 256
+FLAG_STRATIFIED = 512
 
 
 # ---------------------------------------------------------------- structs (hrt.h)
@@ -132,7 +133,7 @@ assert HIT_DTYPE.itemsize == C.sizeof(Hit)
 
 HIP_SYMBOLS = ["hrt_device_count", "hrt_scene_create", "hrt_scene_destroy", "hrt_render_tile", "hrt_render_stripes_device",
                "hrt_render_stripes", "hrt_render_stripes_accumulate_device", "hrt_render_stripes_accumulate", "hrt_stripe_rows", "hrt_stripe_row_index", "hrt_scene_stats", "hrt_resolve_u8",
-               "hrt_resolve_u8_device", "hrt_closest_hit", "hrt_math_probe", "hrt_status_str", "hrt_last_error", "hrt_version",
+               "hrt_resolve_u8_device", "hrt_closest_hit", "hrt_math_probe", "hrt_sampler_probe", "hrt_status_str", "hrt_last_error", "hrt_version",
                "hrt_multi_create", "hrt_multi_destroy", "hrt_multi_devices", "hrt_multi_uses_rccl", "hrt_multi_render", "hrt_bvh_build_device", "hrt_bvh_build_sah",
                "hrt_debug_bounds_violations", "hrt_scene_progress", "hrt_multi_progress",
                "hrt_render_stripes_adaptive_device", "hrt_render_stripes_adaptive", "hrt_adaptive_mean_device", "hrt_env_table_build",
@@ -193,6 +194,7 @@ _hip.hrt_multi_uses_rccl.argtypes = [_vp]
 _hip.hrt_multi_uses_rccl.restype = C.c_int32
 _hip.hrt_multi_render.argtypes = [_vp, C.POINTER(Camera), C.POINTER(Params), C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _u8p, C.POINTER(Stats)]
 _hip.hrt_math_probe.argtypes = [C.c_int, C.c_int32, C.c_int64, _fp, _fp, _fp]
+_hip.hrt_sampler_probe.argtypes = [C.c_int, C.c_uint64, C.c_int64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
 _hip.hrt_env_table_build.argtypes = [_fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp]
 _hip.hrt_emitter_table_build.argtypes = [_vp, C.POINTER(C.c_int64), _fp, _fp, _fp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
 
@@ -242,12 +244,14 @@ def _ptr(a, t=_fp):
 
 # ---------------------------------------------------------------- host side
 def default_params(width, height, samples, quirks=QUIRKS_REFERENCE, seed=0, max_depth=50, stats=False, megakernel=False, timing=False,
-                   thin_lens=False, progress=False, nee=False, nee_env=False, nee_emitters=False, nee_lobes=False):
+                   thin_lens=False, progress=False, nee=False, nee_env=False, nee_emitters=False, nee_lobes=False, stratified=False):
     """nee: next-event estimation with MIS for the scene's rect and sphere lights (FLAG_NEE).
     nee_env: also importance-sample the environment map (FLAG_NEE_ENV); implies nee.
     nee_emitters: sample every rect, box and mesh emitter, wrapped or not, by an alias table (FLAG_NEE_EMITTERS, DESIGN.md 4.7);
     implies nee.
-    nee_lobes: rough metal and medium vertices sample lights too (FLAG_NEE_LOBES); implies nee."""
+    nee_lobes: rough metal and medium vertices sample lights too (FLAG_NEE_LOBES); implies nee.
+    stratified: the samples of a pixel from Owen-scrambled (0,2)-sequences instead of independent Philox words (FLAG_STRATIFIED,
+    DESIGN.md 4.9); combines with every flag but megakernel."""
     p = Params()
     _host.hrt_default_params(C.byref(p), width, height, samples)
     p.quirks = quirks
@@ -256,7 +260,8 @@ def default_params(width, height, samples, quirks=QUIRKS_REFERENCE, seed=0, max_
     p.max_depth = max_depth
     p.flags = (FLAG_STATS if stats else 0) | (FLAG_MEGAKERNEL if megakernel else 0) | (FLAG_TIMING if timing else 0) | \
               (FLAG_THIN_LENS if thin_lens else 0) | (FLAG_PROGRESS if progress else 0) | (FLAG_NEE if nee or nee_env or nee_emitters or nee_lobes else 0) | \
-              (FLAG_NEE_ENV if nee_env else 0) | (FLAG_NEE_EMITTERS if nee_emitters else 0) | (FLAG_NEE_LOBES if nee_lobes else 0)
+              (FLAG_NEE_ENV if nee_env else 0) | (FLAG_NEE_EMITTERS if nee_emitters else 0) | (FLAG_NEE_LOBES if nee_lobes else 0) | \
+              (FLAG_STRATIFIED if stratified else 0)
     return p
 
 
@@ -656,6 +661,15 @@ def math_probe(op, a, b=None, device=0):
         out = np.empty(n, dtype=np.float32)
     bb = _f32(b) if b is not None else None
     _check(_hip.hrt_math_probe(device, op, n, _ptr(a), _ptr(bb) if bb is not None else None, _ptr(out)))
+    return out
+
+
+def sampler_probe(seed, keys, device=0):
+    """FLAG_STRATIFIED's draw on the GPU: keys uint32 [n, 4] = pixel, sample, bounce, purpose | aux << 8 -> uint32 [n, 4] (the words x, y, z, w)."""
+    keys = np.ascontiguousarray(keys, dtype=np.uint32).reshape(-1, 4)
+    out = np.empty_like(keys)
+    u32p = C.POINTER(C.c_uint32)
+    _check(_hip.hrt_sampler_probe(device, seed, len(keys), keys.ctypes.data_as(u32p), out.ctypes.data_as(u32p)))
     return out
 
 

@@ -1177,8 +1177,9 @@ __device__ inline float matscalar_value(const DScene& sc, const hrt_matscalar& m
 #define HRT_NEE_RHO_MIN 0.015625f
 struct NeeLobe { int kind; float rho; vec3 c, nn; };
 // (LOBE is a template parameter, not a test of the pointer: material_scatter<false> is then, statement for statement, the function it
-// was before the lobes, and the kernels of the other flags keep their registers.)
-template <bool LOBE = false>
+// was before the lobes, and the kernels of the other flags keep their registers.  STRAT, HRT_FLAG_STRATIFIED's sampler for the RNG_SCATTER
+// draw (hrt_rng.h strat_draw), is one for the same reason; ball_rand keeps rng_draw.)
+template <bool LOBE = false, bool STRAT = false>
 __device__ inline bool material_scatter(const DScene& sc, const DRec& rec, vec3 rin_d, const rng_ctx& ctx, vec3& emitted,
                                         vec3& attenuation, vec3& so, vec3& sd, bool* lambert = nullptr, NeeLobe* lobe = nullptr) {
     int mat_i = rec.mat;
@@ -1197,7 +1198,7 @@ __device__ inline bool material_scatter(const DScene& sc, const DRec& rec, vec3 
         if (LOBE) lobe->kind = HRT_LOBE_MEDIUM;
         return true;
     }
-    const u32x4 dr = rng_draw(ctx, RNG_SCATTER, 0);
+    const u32x4 dr = rng_draw_as<STRAT>(ctx, RNG_SCATTER, 0);
     const vec3 sph = spherical_rand(dr.x, dr.y);
     if (kind == HRT_MAT_PBR) {  // material.cpp:18-28
         bool metal = length(tex_value(sc, m.mix_tex, rec.u, rec.v, rec.p)) > 0.5f;
@@ -1622,20 +1623,22 @@ struct PathCounters {
 };
 
 // main.cpp:115-123 + Camera::getRay (camera.h:29-39): starts sample `ctx.sample` of pixel (px, py).
+// STRAT (HRT_FLAG_STRATIFIED): jitter and lens from the stratified sampler.
+template <bool STRAT = false>
 __device__ inline void path_begin(const hrt_camera& cam, const hrt_params& pr, int px, int py, rng_ctx& ctx, PathState& ps) {
     const vec3 c_origin(cam.origin[0], cam.origin[1], cam.origin[2]);
     const vec3 c_llc(cam.lower_left[0], cam.lower_left[1], cam.lower_left[2]);
     const vec3 c_hor(cam.horizontal[0], cam.horizontal[1], cam.horizontal[2]);
     const vec3 c_ver(cam.vertical[0], cam.vertical[1], cam.vertical[2]);
     ctx.bounce = 0;
-    const u32x4 j = rng_draw(ctx, RNG_JITTER, 0);
+    const u32x4 j = rng_draw_as<STRAT>(ctx, RNG_JITTER, 0);
     const int x = px;                 // main.cpp:115 (pIdx % W)
     const int y = pr.height - py;     // main.cpp:116 (H - pIdx / W), Q-10
     const float u = ((float)x + linear_rand(j.x, 0.0f, 1.0f)) / (pr.width - 1);
     const float v = ((float)y + linear_rand(j.y, 0.0f, 1.0f)) / (pr.height - 1);
     vec3 offset(0.0f);                                   // camera.h:34-35: the reference's lens offset is 0 ...
     if (pr.flags & HRT_FLAG_THIN_LENS) {                 // ... unless the commented-out circularRand(lensRadius) is asked back
-        const u32x4 l = rng_draw(ctx, RNG_LENS, 0);
+        const u32x4 l = rng_draw_as<STRAT>(ctx, RNG_LENS, 0);
         float rx, ry;
         circular_rand(l.x, cam.lens_radius, rx, ry);
         offset = vec3(cam.lens_u[0], cam.lens_u[1], cam.lens_u[2]) * rx + vec3(cam.lens_v[0], cam.lens_v[1], cam.lens_v[2]) * ry;
@@ -1648,7 +1651,7 @@ __device__ inline void path_begin(const hrt_camera& cam, const hrt_params& pr, i
 // The part of one iteration of main.cpp:43-76 that follows world->hit: background on a miss
 // (main.cpp:47-59), else emitted + scatter (main.cpp:62-75).  Returns true when the path has ended
 // (miss, emitter / absorbed, or MAX_DEPTH segments traced).
-template <bool STATS>
+template <bool STATS, bool STRAT = false>
 __device__ inline bool path_shade(const DScene& sc, const hrt_params& pr, const rng_ctx& ctx, PathState& ps, const WorldHit& wh,
                                   PathCounters& pc) {
     if (wh.prim < 0) {
@@ -1660,7 +1663,7 @@ __device__ inline bool path_shade(const DScene& sc, const hrt_params& pr, const 
     DRec rec;
     hit_record(sc, wh, ps.o, ps.d, pr.quirks, pr.t_min, rec);
     vec3 emitted, attenuation, so, sd;
-    const bool b = material_scatter(sc, rec, ps.d, ctx, emitted, attenuation, so, sd);
+    const bool b = material_scatter<false, STRAT>(sc, rec, ps.d, ctx, emitted, attenuation, so, sd);
     ps.result += ps.atten * emitted;
     if (!b) return true;
     ps.atten *= attenuation;

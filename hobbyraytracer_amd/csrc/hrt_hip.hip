@@ -17,6 +17,7 @@
 //   k_wf_shade<STATS, true, true> / k_wf_shadow<true> / k_env_rows / k_env_marginal   environment-map sampling, HRT_FLAG_NEE_ENV (4.6).
 //   k_wf_shade<STATS, true, ENV, true> / k_wf_shadow<ENV, true>   the emitter table, HRT_FLAG_NEE_EMITTERS (4.7).
 //   k_wf_shade<STATS, true, ENV, EMIT, true> / k_wf_shadow<ENV, EMIT, true>   light samples at rough metal and medium vertices, HRT_FLAG_NEE_LOBES (4.8).
+//   k_wf_gen_st / k_wf_shade_st / k_wf_shadow_st (the same template arguments)   the stratified sampler, HRT_FLAG_STRATIFIED (4.9): hrt_wf_kernels.h.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>   // types and prototypes only: the library is loaded on demand (rccl_api below)
 #include <dlfcn.h>
@@ -269,6 +270,16 @@ __global__ void k_math_probe(int op, long long n, const float* __restrict__ in, 
     }
 }
 
+// hrt_sampler_probe: the stratified draw (hrt_rng.h strat_draw) of n keys (pixel, sample, bounce, purpose | aux << 8)
+__global__ __launch_bounds__(256) void k_sampler_probe(uint32_t seed_lo, uint32_t seed_hi, long long n, const uint4* __restrict__ keys, uint4* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint4 k = keys[i];
+    rng_ctx ctx; ctx.seed_lo = seed_lo; ctx.seed_hi = seed_hi; ctx.pixel = k.x; ctx.sample = k.y; ctx.bounce = k.z;
+    const u32x4 r = strat_draw(ctx, k.w & 0xFFu, k.w >> 8);
+    out[i] = make_uint4(r.x, r.y, r.z, r.w);
+}
+
 // ===================================================================== wavefront pipeline (default path)
 // The same render() as k_pathtrace, organised for wave density instead of per-lane persistence:
 //   * every (pixel, sample) of the batch owns a SLOT (the 288 GB of HBM make a whole 640x640x100 frame
@@ -513,45 +524,7 @@ __device__ inline void wf_ref_publish(const WfBuf& w, unsigned task, unsigned rc
     const unsigned k = atomicAdd(&w.ref_prod[g], 1u);
     w.ref_list[(size_t)g * w.ref_cap + k] = make_uint2(task, rcount);
 }
-// Camera rays (main.cpp:115-123) of every slot of the batch + the preparation of their first segment.
-template <bool STATS>
-__global__ __launch_bounds__(256) void k_wf_gen(DScene sc, hrt_camera cam, hrt_params pr, RenderMap map, WfScene ws, unsigned n_local, int s0,
-                                                unsigned n_slots, WfBuf w, DeviceCounters* counters) {
-    const unsigned lane = threadIdx.x & 63u;
-    const unsigned wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
-    const unsigned long long lt = (1ull << lane) - 1ull;
-    unsigned n_culled = 0;
-    HRT_FOR_MY_TASKS(task, w, wave, lane) {
-        const unsigned base = task * w.T;
-        const unsigned n = base < n_slots ? min(w.T, n_slots - base) : 0u;
-        unsigned qpos = base, rcount = 0;
-        for (unsigned j0 = 0; j0 < n; j0 += 64) {
-            const unsigned j = j0 + lane;
-            int enq = HRT_ENQ_NONE;
-            MeshRay mr;
-            float closest = __builtin_huge_valf();
-            const unsigned slot = base + j;
-            if (j < n) {
-                int px, py;
-                const unsigned sl = fastdiv(slot, n_local, map.m_nl);
-                slot_pixel(map, slot - sl * n_local, px, py);
-                rng_ctx ctx; ctx.seed_lo = pr.seed_lo; ctx.seed_hi = pr.seed_hi;
-                ctx.pixel = (uint32_t)(py * pr.width + px); ctx.sample = (uint32_t)(s0 + (int)sl); ctx.bounce = 0;
-                PathState ps;
-                path_begin(cam, pr, px, py, ctx, ps);
-                int prim = -1, sub = -1;
-                enq = wf_prepare<STATS>(sc, pr, 0, ws.first_mesh, ws.has_mesh ? ws.first_mesh : -1, ps.o, ps.d, ctx, closest, prim, sub, mr, n_culled);
-                wf_store_state(w, 0, slot, ps, closest, slot, prim, sub);
-            }
-            wf_enqueue(w, enq, mr, closest, slot, lt, qpos, base + w.T - 1, rcount);
-        }
-        if (lane == 0) { w.live[task] = n; w.qn[task] = qpos - base; w.rn[task] = rcount; if (rcount) wf_ref_publish(w, task, rcount); }
-    }
-    if (STATS) {
-        const unsigned c = wave_sum(n_culled);
-        if (lane == 0 && c) atomicAdd(&counters->box_tests, 2ull * c);   // the root's two boxes were tested
-    }
-}
+// (k_wf_gen, the camera rays of every slot of a batch: hrt_wf_kernels.h, included below)
 
 // ---- the three per-round stages as WAVE-LEVEL functions over one task; the kernels below (one launch per stage per
 // ---- round, or k_wf_tail: every remaining round of a task in one go) only differ in how a wave comes by its tasks.
@@ -1067,7 +1040,7 @@ __device__ inline void missq_flush(const DScene& sc, const WfBuf& w, MissQueue& 
 // read (nrec: shading normal, p_b of the new direction or -1).  The light sample itself is k_wf_shadow's.
 // EMIT (HRT_FLAG_NEE_EMITTERS): the light is an entry of the emitter table, emit_base[prim] + the hit's triangle
 // index (through sub_tri) or box side; q from its shade-side record.
-template <bool STATS, bool EMIT = false>
+template <bool STATS, bool EMIT = false, bool STRAT = false>
 __device__ HRT_WAVE_FN bool path_shade_nee(const DScene& sc, const hrt_params& pr, const WfBuf& w, const rng_ctx& ctx, PathState& ps,
                                            const WorldHit& wh, PathCounters& pc, float prev_pb, float4& nrec) {
     if (STATS && sc.lprims[wh.prim].kind == HRT_PRIM_MESH) pc.mesh_hits++;
@@ -1075,7 +1048,7 @@ __device__ HRT_WAVE_FN bool path_shade_nee(const DScene& sc, const hrt_params& p
     hit_record(sc, wh, ps.o, ps.d, pr.quirks, pr.t_min, rec);
     vec3 emitted, attenuation, so, sd;
     bool lambert = false;
-    const bool b = material_scatter(sc, rec, ps.d, ctx, emitted, attenuation, so, sd, &lambert);
+    const bool b = material_scatter<false, STRAT>(sc, rec, ps.d, ctx, emitted, attenuation, so, sd, &lambert);
     if (EMIT && !b && prev_pb >= 0.0f) {
         int li = w.emit_base[wh.prim];
         if (li >= 0) {
@@ -1116,7 +1089,7 @@ __device__ HRT_WAVE_FN bool path_shade_nee(const DScene& sc, const hrt_params& p
 // always were, and keep their registers -- tests/test_nee_emitters_resources.py.  The weighting of `emitted` below is path_shade_nee's,
 // statement for statement: moving it into a helper both call gave k_wf_shade<true, true, true> 8 B of scratch
 // (tests/test_env_nee_resources.py), so a change to one of the two copies must be made to the other.)
-template <bool STATS, bool EMIT>
+template <bool STATS, bool EMIT, bool STRAT = false>
 __device__ HRT_WAVE_FN bool path_shade_lobes(const DScene& sc, const hrt_params& pr, const WfBuf& w, const rng_ctx& ctx, PathState& ps,
                                            const WorldHit& wh, PathCounters& pc, float prev_pb, float4& nrec, float4& mrec) {
     if (STATS && sc.lprims[wh.prim].kind == HRT_PRIM_MESH) pc.mesh_hits++;
@@ -1125,7 +1098,7 @@ __device__ HRT_WAVE_FN bool path_shade_lobes(const DScene& sc, const hrt_params&
     vec3 emitted, attenuation, so, sd;
     bool lambert = false;
     NeeLobe lobe; lobe.kind = HRT_LOBE_NONE;
-    const bool b = material_scatter<true>(sc, rec, ps.d, ctx, emitted, attenuation, so, sd, &lambert, &lobe);
+    const bool b = material_scatter<true, STRAT>(sc, rec, ps.d, ctx, emitted, attenuation, so, sd, &lambert, &lobe);
     if (EMIT && !b && prev_pb >= 0.0f) {
         int li = w.emit_base[wh.prim];
         if (li >= 0) {
@@ -1171,7 +1144,7 @@ __device__ HRT_WAVE_FN bool path_shade_lobes(const DScene& sc, const hrt_params&
     return ps.bounce >= pr.max_depth;
 }
 
-template <bool STATS, bool NEE = false, bool ENV = false, bool EMIT = false, bool LOBES = false>
+template <bool STATS, bool NEE = false, bool ENV = false, bool EMIT = false, bool LOBES = false, bool STRAT = false>
 __device__ HRT_WAVE_FN void wf_shade_task(const DScene& sc, const hrt_params& pr, const RenderMap& map, const WfScene& ws, unsigned n_local, int s0, int round,
                                      const WfBuf& w, unsigned task, unsigned n, unsigned lane, unsigned long long lt, MissQueue& mq,
                                      PathCounters& pc, unsigned& n_seg, unsigned& n_culled, unsigned& live_out, unsigned& qn_out, unsigned& rn_out) {
@@ -1226,11 +1199,11 @@ __device__ HRT_WAVE_FN void wf_shade_task(const DScene& sc, const hrt_params& pr
         if (LOBES) mrec = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         if (j0 + lane < n && !missed) {
             bool ended;
-            if (LOBES) ended = path_shade_lobes<STATS, EMIT>(sc, pr, w, ctx, ps, wh, pc, ENV ? prev_pb : (round > 0 ? w.N[par][HRT_NREC(pos)].w : -1.0f), nrec, mrec);
-            else if (ENV) ended = path_shade_nee<STATS, EMIT>(sc, pr, w, ctx, ps, wh, pc, prev_pb, nrec);
-            else if (EMIT) ended = path_shade_nee<STATS, true>(sc, pr, w, ctx, ps, wh, pc, round > 0 ? w.N[par][pos].w : -1.0f, nrec);
-            else if (NEE) ended = path_shade_nee<STATS>(sc, pr, w, ctx, ps, wh, pc, round > 0 ? w.N[par][pos].w : -1.0f, nrec);
-            else ended = path_shade<STATS>(sc, pr, ctx, ps, wh, pc);
+            if (LOBES) ended = path_shade_lobes<STATS, EMIT, STRAT>(sc, pr, w, ctx, ps, wh, pc, ENV ? prev_pb : (round > 0 ? w.N[par][HRT_NREC(pos)].w : -1.0f), nrec, mrec);
+            else if (ENV) ended = path_shade_nee<STATS, EMIT, STRAT>(sc, pr, w, ctx, ps, wh, pc, prev_pb, nrec);
+            else if (EMIT) ended = path_shade_nee<STATS, true, STRAT>(sc, pr, w, ctx, ps, wh, pc, round > 0 ? w.N[par][pos].w : -1.0f, nrec);
+            else if (NEE) ended = path_shade_nee<STATS, false, STRAT>(sc, pr, w, ctx, ps, wh, pc, round > 0 ? w.N[par][pos].w : -1.0f, nrec);
+            else ended = path_shade<STATS, STRAT>(sc, pr, ctx, ps, wh, pc);
             if (ended) w.rad[slot] = make_float4(ps.result.x, ps.result.y, ps.result.z, 0.0f);
             else {
                 alive = true;
@@ -1283,33 +1256,7 @@ __device__ HRT_WAVE_FN void wf_shade_counters(const WfBuf& w, DeviceCounters* co
 #ifndef HRT_SHADE_WAVES
 #define HRT_SHADE_WAVES 4   // waves per SIMD the register allocator must leave room for (<= 128 VGPRs)
 #endif
-// ENV (HRT_FLAG_NEE_ENV, with NEE only): the environment map's MIS weight on escapes from eligible vertices
-// EMIT (HRT_FLAG_NEE_EMITTERS, with NEE only): the MIS weight of emission found on any entry of the emitter table
-// LOBES (HRT_FLAG_NEE_LOBES, with NEE only): rough Metal and Isotropic vertices are eligible too
-template <bool STATS, bool NEE, bool ENV = false, bool EMIT = false, bool LOBES = false>
-__global__ __launch_bounds__(256, HRT_SHADE_WAVES) void k_wf_shade(DScene sc, hrt_params pr, RenderMap map, WfScene ws, unsigned n_local, int s0, int round,
-                                                  WfBuf w, DeviceCounters* counters) {
-    const unsigned lane = threadIdx.x & 63u;
-    const unsigned wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const unsigned long long lt = (1ull << lane) - 1ull;
-    __shared__ __attribute__((aligned(16))) uint32_t s_tables[HRT_TABLE_LDS_BYTES / 4];
-    __shared__ float s_missq[4][(ENV ? 8 : 7) * HRT_MISSQ_CAP];
-#ifdef HRT_SHADE_PROFILE
-    g_prof_counters = counters;
-#endif
-    stage_tables(sc, s_tables);
-    MissQueue mq;
-    mq.f = s_missq[threadIdx.x >> 6]; mq.slot = (unsigned*)(mq.f + (ENV ? 7 : 6) * HRT_MISSQ_CAP); mq.count = 0;
-    unsigned n_seg = 0, n_culled = 0;
-    PathCounters pc; pc.rays = 0; pc.samples = 0; pc.mesh_hits = 0; pc.env_lookups = 0; pc.bvh.box_tests = 0; pc.bvh.tri_tests = 0;
-    HRT_FOR_MY_TASKS(task, w, wave, lane) {
-        unsigned live, qn, rn;
-        wf_shade_task<STATS, NEE, ENV, EMIT, LOBES>(sc, pr, map, ws, n_local, s0, round, w, task, HRT_UNIFORM(w.live[task]), lane, lt, mq, pc, n_seg, n_culled, live, qn, rn);
-        if (lane == 0) { w.live[task] = live; w.qn[task] = qn; w.rn[task] = rn; if (rn) wf_ref_publish(w, task, rn); }
-    }
-    if (mq.count) missq_flush<STATS, ENV>(sc, w, mq, lane, mq.count, pc);
-    wf_shade_counters<STATS>(w, counters, wave, lane, n_seg, n_culled, pc);
-}
+// (k_wf_shade: hrt_wf_kernels.h, included below)
 
 // HRT_FLAG_NEE, after round `round`'s k_wf_shade: for every survivor whose vertex is eligible (a Lambertian scatter: N.w >= 0), one
 // light sample.  Light and point from one RNG_LIGHT draw keyed by (pixel, sample, round); the shadow ray is the ray the bounce would
@@ -1338,147 +1285,18 @@ __global__ __launch_bounds__(256, HRT_SHADE_WAVES) void k_wf_shade(DScene sc, hr
 // (nee_vertex_inv_acc).  -DHRT_LOBES_NO_ACC (experiment only): without that division, kept compilable so the tests can be
 // shown to catch it.
 #define HRT_SHADOWQ_CAP 128
-template <bool ENV, bool EMIT = false, bool LOBES = false>
-__global__ __launch_bounds__(HRT_BLOCK) void k_wf_shadow(DScene sc, hrt_params pr, RenderMap map, unsigned n_local, int s0, int round, WfBuf w) {
-    __shared__ int s_stack[HRT_STACK_DEPTH * HRT_BLOCK];
-    __shared__ __attribute__((aligned(16))) uint32_t s_tables[HRT_TABLE_LDS_BYTES / 4];
-    __shared__ unsigned s_queue[HRT_BLOCK / 64][HRT_SHADOWQ_CAP];
-    int* stack = s_stack + threadIdx.x;
-    stage_tables(sc, s_tables);
-    const unsigned lane = threadIdx.x & 63u;
-    const unsigned wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    unsigned* const q = s_queue[threadIdx.x >> 6];
-    const int nxt = (round + 1) & 1;
-    unsigned n_shadow = 0;
-    unsigned qn = 0;                          // wave-uniform queue length
-    TaskPuller puller = HRT_TASK_PULLER(wave, w.n_groups);
-    unsigned task = 0, j0 = 0, n = 0;
-    bool have = wf_next_task(w, puller, lane, task);
-    if (have) n = HRT_UNIFORM(w.live[task]);
-    for (;;) {
-        // fill: whole 64-position chunks of this wave's tasks until 64 eligible positions wait (or the tasks are done)
-        while (have && qn < 64) {
-            if (j0 >= n) {
-                have = wf_next_task(w, puller, lane, task);
-                j0 = 0;
-                n = have ? HRT_UNIFORM(w.live[task]) : 0u;
-                continue;
-            }
-            const unsigned pos = task * w.T + j0 + lane;
-            const bool elig = j0 + lane < n && w.N[nxt][HRT_NREC(pos)].w >= 0.0f;
-            const unsigned long long m = __ballot(elig);
-            if (elig) q[qn + lanes_below(m)] = pos;
-            qn += (unsigned)__popcll(m);          // < 64 + 64 <= HRT_SHADOWQ_CAP
-            j0 += 64;
-        }
-        const unsigned k = qn < 64 ? qn : 64u;
-        if (k == 0) break;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        const unsigned pos = lane < k ? q[qn - k + lane] : 0u;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        qn -= k;
-        if (lane >= k) continue;
-        const float4 nr = w.N[nxt][HRT_NREC(pos)];
-        const float4 mr = LOBES ? w.N[nxt][HRT_NREC(pos) + 1] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-#ifdef HRT_LOBES_NO_ACC   // experiment only: no correction for the bounce's survival -- the biased estimator
-        const float inv_acc = 1.0f;
-#else
-        const float inv_acc = LOBES ? nee_vertex_inv_acc(nr, mr) : 1.0f;
-#endif     // a Metal vertex samples only when its bounce survived
-        const float4 a = w.S0[nxt][pos], b = w.S1[nxt][pos];
-        const float az = w.S3[nxt][pos];
-        const unsigned slot = __float_as_uint(w.S2[nxt][pos].w);
-        const vec3 x(a.x, a.y, a.z);
-        [&]() {   // the table-light sample (a lambda: `return` ends it, and the environment sample below still runs)
-            if (ENV && (EMIT ? w.n_emit : w.n_lights) == 0) return;
-            rng_ctx ctx = slot_ctx(pr, map, slot, n_local, s0, round);
-            const u32x4 u = rng_draw(ctx, RNG_LIGHT, 0);
-            if (EMIT) {
-                const int li = emit_choose(w.emit_alias, w.n_emit, u.x, rng_draw(ctx, RNG_LIGHT, 1).x);
-                const float4 E0 = w.emit_rec[HRT_EMIT_REC * li], E1 = w.emit_rec[HRT_EMIT_REC * li + 1], E2 = w.emit_rec[HRT_EMIT_REC * li + 2];
-                vec3 wd;
-                float pl, reach;
-                const int kind = __float_as_int(E0.y);
-                const bool ok = kind == HRT_PRIM_SPHERE ? nee_sample(E0, E1, E2, x, u.y, u.z, wd, pl, reach)
-                                                        : emit_sample_planar(kind == HRT_EMIT_TRI, E1, E2, w.emit_rec[HRT_EMIT_REC * li + 3], x, u.y, u.z, wd, pl, reach);
-                if (!ok) return;
-                float t0, t1;
-                const float pb = LOBES ? nee_vertex_pdf(nr, mr, wd, t0, t1) : nee_bsdf_pdf(vec3(nr.x, nr.y, nr.z), wd, t0, t1);
-                if (!(pb > 0.0f)) return;
-                const float tk = LOBES ? nee_vertex_len(mr.w, nee_pick_root(t0, t1, u.w), u.w) : nee_pick_root(t0, t1, u.w);
-                if (LOBES && !(tk > 0.0f)) return;
-                const vec3 d = tk * wd;
-#ifdef HRT_EMIT_EUCLID_TMAX
-                const float t_max = reach / tk * 1.001f;
-#else
-                const float t_max = E2.w != 0.0f ? __builtin_huge_valf() : reach / tk * 1.001f;   // E2.w: wrapped
-#endif
-                ctx.bounce = (uint32_t)round | HRT_RNG_SHADOW;
-                ++n_shadow;
-                DCounters cnt; cnt.box_tests = 0; cnt.tri_tests = 0;
-                const WorldHit wh = world_hit<false>(sc, x, d, pr.t_min, t_max, pr.quirks, ctx, stack, cnt);
-                const int esub = __float_as_int(E0.w);
-                if (wh.prim != __float_as_int(E0.x) || (esub >= 0 && sub_tri(wh.sub) != esub)) return;
-                DRec rec;
-                hit_record(sc, wh, x, d, pr.quirks, pr.t_min, rec);
-                const vec3 term = vec3(b.z, b.w, az) * nee_emitted(sc, rec) * (LOBES ? nee_mis_shadow(pb, E0.z * pl) * inv_acc : nee_mis_shadow(pb, E0.z * pl));
-                const float4 acc = w.direct[slot];
-                w.direct[slot] = make_float4(acc.x + term.x, acc.y + term.y, acc.z + term.z, 0.0f);
-                return;
-            }
-            const int li = nee_choose(w.lights, w.n_lights, u.x);
-            const float4 L0 = w.lights[HRT_NEE_REC * li], L1 = w.lights[HRT_NEE_REC * li + 1], L2 = w.lights[HRT_NEE_REC * li + 2];
-            vec3 wd;
-            float pl, reach;
-            if (!nee_sample(L0, L1, L2, x, u.y, u.z, wd, pl, reach)) return;
-            float t0, t1;
-            const float pb = LOBES ? nee_vertex_pdf(nr, mr, wd, t0, t1) : nee_bsdf_pdf(vec3(nr.x, nr.y, nr.z), wd, t0, t1);
-            if (!(pb > 0.0f)) return;
-#ifdef HRT_NEE_UNIT_SHADOW
-            const float tk = 1.0f;
-#else
-            const float tk = LOBES ? nee_vertex_len(mr.w, nee_pick_root(t0, t1, u.w), u.w) : nee_pick_root(t0, t1, u.w);
-            if (LOBES && !(tk > 0.0f)) return;
-#endif
-            const vec3 d = tk * wd;
-            ctx.bounce = (uint32_t)round | HRT_RNG_SHADOW;
-            ++n_shadow;
-            DCounters cnt; cnt.box_tests = 0; cnt.tri_tests = 0;
-            const WorldHit wh = world_hit<false>(sc, x, d, pr.t_min, reach / tk * 1.001f, pr.quirks, ctx, stack, cnt);
-            if (wh.prim != __float_as_int(L0.x)) return;
-            DRec rec;
-            hit_record(sc, wh, x, d, pr.quirks, pr.t_min, rec);
-            const vec3 term = vec3(b.z, b.w, az) * nee_emitted(sc, rec) * (LOBES ? nee_mis_shadow(pb, L0.z * pl) * inv_acc : nee_mis_shadow(pb, L0.z * pl));
-            const float4 acc = w.direct[slot];
-            w.direct[slot] = make_float4(acc.x + term.x, acc.y + term.y, acc.z + term.z, 0.0f);
-        }();
-        if (ENV) {   // the environment sample of the same vertex
-            rng_ctx ctx = slot_ctx(pr, map, slot, n_local, s0, round);
-            vec3 we;
-            float pe, t0, t1;
-            int ci, cj;
-            if (!env_sample(w.env_marg, w.env_cond, w.env_w, w.env_h, rng_draw(ctx, RNG_ENV, 0), we, pe, ci, cj)) continue;
-            const float pb = LOBES ? nee_vertex_pdf(nr, mr, we, t0, t1) : nee_bsdf_pdf(vec3(nr.x, nr.y, nr.z), we, t0, t1);
-            if (!(pb > 0.0f)) continue;
-            const uint32_t ur = rng_draw(ctx, RNG_ENV, 1).x;
-            const float te = LOBES ? nee_vertex_len(mr.w, nee_pick_root(t0, t1, ur), ur) : nee_pick_root(t0, t1, ur);
-            if (LOBES && !(te > 0.0f)) continue;
-            const vec3 d = te * we;
-            pe = env_pdf(w.env_marg, w.env_cond, w.env_w, w.env_h, d);   // the density of the texel background_value reads for d
-            if (!(pe > 0.0f)) continue;
-            ctx.bounce = (uint32_t)round | HRT_RNG_SHADOW | HRT_RNG_SHADOW_ENV;
-            ++n_shadow;
-            DCounters cnt; cnt.box_tests = 0; cnt.tri_tests = 0;
-            const WorldHit wh = world_hit<false>(sc, x, d, pr.t_min, __builtin_huge_valf(), pr.quirks, ctx, stack, cnt);
-            if (wh.prim >= 0) continue;
-            const vec3 term = vec3(b.z, b.w, az) * background_value(sc, d) * (LOBES ? nee_mis_shadow(pb, pe) * inv_acc : nee_mis_shadow(pb, pe));
-            const float4 acc = w.direct[slot];
-            w.direct[slot] = make_float4(acc.x + term.x, acc.y + term.y, acc.z + term.z, 0.0f);
-        }
-    }
-    const unsigned c = wave_sum(n_shadow);
-    if (lane == 0 && c) w.wave_shadow[wave] += (unsigned long long)c;      // this wave's own cell
-}
+// k_wf_gen / k_wf_shade / k_wf_shadow and their HRT_FLAG_STRATIFIED twins k_wf_gen_st / k_wf_shade_st / k_wf_shadow_st:
+// one text, compiled once per sampler
+#define HRT_K(name) name
+#define HRT_STRAT false
+#include "hrt_wf_kernels.h"
+#undef HRT_K
+#undef HRT_STRAT
+#define HRT_K(name) name##_st
+#define HRT_STRAT true
+#include "hrt_wf_kernels.h"
+#undef HRT_K
+#undef HRT_STRAT
 
 // HRT_FLAG_NEE_ENV's sampling table (hrt_device.h env_*).  One CDF of n float64 weights per block of 256 threads, in a fixed
 // order and without atomics, so that every device builds the same bits: thread t sums the contiguous run [t c, (t + 1) c) of the weights
@@ -2127,6 +1945,7 @@ hrt_status check_params(const hrt_params* p) {
     if ((p->flags & HRT_FLAG_NEE_EMITTERS) && !(p->flags & HRT_FLAG_NEE)) return fail(HRT_ERR_INVALID, "HRT_FLAG_NEE_EMITTERS needs HRT_FLAG_NEE");
     if ((p->flags & HRT_FLAG_NEE_LOBES) && !(p->flags & HRT_FLAG_NEE)) return fail(HRT_ERR_INVALID, "HRT_FLAG_NEE_LOBES needs HRT_FLAG_NEE");
     if ((p->flags & HRT_FLAG_MEGAKERNEL) && (p->flags & HRT_FLAG_NEE)) return fail(HRT_ERR_UNSUPPORTED, "next-event estimation renders on the wavefront pipeline only");
+    if ((p->flags & HRT_FLAG_MEGAKERNEL) && (p->flags & HRT_FLAG_STRATIFIED)) return fail(HRT_ERR_UNSUPPORTED, "the stratified sampler renders on the wavefront pipeline only");
     return HRT_OK;
 }
 
@@ -2272,6 +2091,8 @@ hrt_status launch_wavefront(hrt_scene* sc, const hrt_camera* cam, const hrt_para
     const bool nee = (pr->flags & HRT_FLAG_NEE) != 0 && (sc->n_lights > 0 || env || emit);
     // HRT_FLAG_NEE_LOBES widens which vertices sample whatever the flags above sample: nothing to sample, nothing to widen.
     const bool lobes = nee && (pr->flags & HRT_FLAG_NEE_LOBES) != 0;
+    // HRT_FLAG_STRATIFIED: the k_wf_*_st kernels, whose jitter, lens, scatter, light and environment draws are strat_draw's
+    const bool strat = (pr->flags & HRT_FLAG_STRATIFIED) != 0;
     size_t cap = wf_max_slots(sc, nee, lobes);
     const int s_end = s_first + s_count;
     int chunk = (int)std::min<size_t>((size_t)s_count, std::max<size_t>(1, cap / n_local));
@@ -2314,6 +2135,7 @@ hrt_status launch_wavefront(hrt_scene* sc, const hrt_camera* cam, const hrt_para
     const bool stale_ff = sc->ds.stale_ff && (pr->quirks & HRT_Q3_TRI_NO_FACE);
     if (stale_ff) tail_round = D;        // k_wf_tail has no stage for the stale frontFace (k_wf_stale): round by round
     if (nee) tail_round = D;             // ... nor for the light samples (k_wf_shadow)
+    if (strat) tail_round = D;           // ... nor the stratified sampler (k_wf_shade_st)
     tail_round = std::min(tail_round, D);
     int leaf_num = 48;                                   // k_wf_ext: start the leaf phase when >= 48/64 of the busy lanes wait at a leaf
     if (const char* e = getenv("HRT_EXT_LEAF_NUM")) leaf_num = atoi(e);
@@ -2383,7 +2205,7 @@ hrt_status launch_wavefront(hrt_scene* sc, const hrt_camera* cam, const hrt_para
         next_counters((unsigned)task_blocks * 4u);
         w.ref_prod = ref_block(0, 0); w.ref_cons = ref_block(D, 0);
         with_bool(stats, [&](auto S) {
-            hipLaunchKernelGGL(k_wf_gen<decltype(S)::value>, dim3(task_blocks), dim3(256), 0, stream, sc->ds, *cam, *pr, map, ws, n_local, s0, n_slots, w, sc->d_counters);
+            hipLaunchKernelGGL(strat ? k_wf_gen_st<decltype(S)::value> : k_wf_gen<decltype(S)::value>, dim3(task_blocks), dim3(256), 0, stream, sc->ds, *cam, *pr, map, ws, n_local, s0, n_slots, w, sc->d_counters);
         });
         for (int r = 0; r < tail_round; ++r) {
             const int par = r & 1;
@@ -2418,22 +2240,22 @@ hrt_status launch_wavefront(hrt_scene* sc, const hrt_camera* cam, const hrt_para
             w.ref_prod = ref_block(r + 1, 0); w.ref_cons = ref_block(D, 0);
             if (lobes) {
                 with_bool(env, [&](auto E) { with_bool(emit, [&](auto M) { with_bool(stats, [&](auto S) {
-                    hipLaunchKernelGGL((k_wf_shade<decltype(S)::value, true, decltype(E)::value, decltype(M)::value, true>), dim3(task_blocks), dim3(256), 0, stream, sc->ds, *pr,
+                    hipLaunchKernelGGL((strat ? k_wf_shade_st<decltype(S)::value, true, decltype(E)::value, decltype(M)::value, true> : k_wf_shade<decltype(S)::value, true, decltype(E)::value, decltype(M)::value, true>), dim3(task_blocks), dim3(256), 0, stream, sc->ds, *pr,
                                        map, ws, n_local, s0, r, w, sc->d_counters);
                 }); }); });
             } else if (emit) {
                 with_bool(env, [&](auto E) { with_bool(stats, [&](auto S) {
-                    hipLaunchKernelGGL((k_wf_shade<decltype(S)::value, true, decltype(E)::value, true>), dim3(task_blocks), dim3(256), 0, stream, sc->ds, *pr, map, ws,
+                    hipLaunchKernelGGL((strat ? k_wf_shade_st<decltype(S)::value, true, decltype(E)::value, true> : k_wf_shade<decltype(S)::value, true, decltype(E)::value, true>), dim3(task_blocks), dim3(256), 0, stream, sc->ds, *pr, map, ws,
                                        n_local, s0, r, w, sc->d_counters);
                 }); });
             } else if (env) {
                 with_bool(stats, [&](auto S) {
-                    hipLaunchKernelGGL((k_wf_shade<decltype(S)::value, true, true>), dim3(task_blocks), dim3(256), 0, stream, sc->ds, *pr, map, ws, n_local, s0, r, w,
+                    hipLaunchKernelGGL((strat ? k_wf_shade_st<decltype(S)::value, true, true> : k_wf_shade<decltype(S)::value, true, true>), dim3(task_blocks), dim3(256), 0, stream, sc->ds, *pr, map, ws, n_local, s0, r, w,
                                        sc->d_counters);
                 });
             } else {
                 with_bool(nee, [&](auto N) { with_bool(stats, [&](auto S) {
-                    hipLaunchKernelGGL((k_wf_shade<decltype(S)::value, decltype(N)::value>), dim3(task_blocks), dim3(256), 0, stream, sc->ds, *pr, map, ws, n_local, s0, r, w,
+                    hipLaunchKernelGGL((strat ? k_wf_shade_st<decltype(S)::value, decltype(N)::value> : k_wf_shade<decltype(S)::value, decltype(N)::value>), dim3(task_blocks), dim3(256), 0, stream, sc->ds, *pr, map, ws, n_local, s0, r, w,
                                        sc->d_counters);
                 }); });
             }
@@ -2442,12 +2264,14 @@ hrt_status launch_wavefront(hrt_scene* sc, const hrt_camera* cam, const hrt_para
                 next_counters((unsigned)task_blocks * 4u);
                 if (lobes)
                     with_bool(env, [&](auto E) { with_bool(emit, [&](auto M) {
-                        hipLaunchKernelGGL((k_wf_shadow<decltype(E)::value, decltype(M)::value, true>), dim3(task_blocks), dim3(HRT_BLOCK), 0, stream, sc->ds, *pr, map, n_local, s0, r, w);
+                        hipLaunchKernelGGL((strat ? k_wf_shadow_st<decltype(E)::value, decltype(M)::value, true> : k_wf_shadow<decltype(E)::value, decltype(M)::value, true>), dim3(task_blocks), dim3(HRT_BLOCK), 0, stream, sc->ds, *pr, map, n_local, s0, r, w);
                     }); });
                 else if (emit)
-                    hipLaunchKernelGGL((env ? k_wf_shadow<true, true> : k_wf_shadow<false, true>), dim3(task_blocks), dim3(HRT_BLOCK), 0, stream, sc->ds, *pr, map, n_local, s0, r, w);
+                    hipLaunchKernelGGL((strat ? (env ? k_wf_shadow_st<true, true> : k_wf_shadow_st<false, true>) : (env ? k_wf_shadow<true, true> : k_wf_shadow<false, true>)),
+                                       dim3(task_blocks), dim3(HRT_BLOCK), 0, stream, sc->ds, *pr, map, n_local, s0, r, w);
                 else
-                    hipLaunchKernelGGL(env ? k_wf_shadow<true> : k_wf_shadow<false>, dim3(task_blocks), dim3(HRT_BLOCK), 0, stream, sc->ds, *pr, map, n_local, s0, r, w);
+                    hipLaunchKernelGGL((strat ? (env ? k_wf_shadow_st<true> : k_wf_shadow_st<false>) : (env ? k_wf_shadow<true> : k_wf_shadow<false>)),
+                                       dim3(task_blocks), dim3(HRT_BLOCK), 0, stream, sc->ds, *pr, map, n_local, s0, r, w);
             }
             if (progress)   // paths ended so far = earlier batches + this batch's slots - the live ones (w.live, as k_wf_shade left it)
                 hipLaunchKernelGGL(k_wf_progress, dim3(1), dim3(256), 0, stream, w.live, w.n_tasks, sc->progress_base + n_slots, sc->d_progress);
@@ -3083,6 +2907,23 @@ hrt_status hrt_math_probe(int device, int32_t op, int64_t n, const float* in, co
     HRT_API_CATCH
 }
 
+hrt_status hrt_sampler_probe(int device, uint64_t seed, int64_t n, const uint32_t* keys, uint32_t* out) {
+    HRT_API_TRY
+    if (!keys || !out || n < 0) return fail(HRT_ERR_INVALID, "bad argument");
+    if (n == 0) return HRT_OK;
+    HIPCHK(hipSetDevice(device));
+    DevBuf d_keys, d_out;
+    HRTCHK(d_keys.alloc((size_t)n * 16, "hipMalloc"));
+    HRTCHK(d_out.alloc((size_t)n * 16, "hipMalloc"));
+    hipError_t e;
+    if ((e = hipMemcpy(d_keys.get(), keys, (size_t)n * 16, hipMemcpyHostToDevice)) != hipSuccess) return fail_hip(e, "hipMemcpy");
+    hipLaunchKernelGGL(k_sampler_probe, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, (uint32_t)seed, (uint32_t)(seed >> 32), (long long)n,
+                       d_keys.get<const uint4>(), d_out.get<uint4>());
+    if ((e = hipGetLastError()) != hipSuccess) return fail_hip(e, "k_sampler_probe launch");
+    if ((e = hipMemcpy(out, d_out.get(), (size_t)n * 16, hipMemcpyDeviceToHost)) != hipSuccess) return fail_hip(e, "hipMemcpy D2H");
+    return HRT_OK;
+    HRT_API_CATCH
+}
 
 // ---------------------------------------------------------------- multi-GPU session: scene replicated on the
 // devices of this process, image rows dealt in interleaved blocks, one RCCL gather of the device-resident stripes over xGMI

@@ -42,6 +42,8 @@ constexpr uint64_t kNeeEnvHashSalt = 0x4e45452d454e5621ull;   // "NEE-ENV!"
 constexpr uint64_t kNeeEmittersHashSalt = 0x4e45452d454d4954ull;   // "NEE-EMIT"
 // ... and one with --nee-lobes its own, on top of whichever of the above applies
 constexpr uint64_t kNeeLobesHashSalt = 0x4e45452d4c4f4245ull;   // "NEE-LOBE"
+// ... and one with --stratified its own, whatever the estimator: its sums continue a sequence, not a stream of independent samples
+constexpr uint64_t kStratifiedHashSalt = 0x535452415449464cull;   // "STRATIFL"
 // FNV-1a over everything the kernels read of the scene (hrt_flat_scene's arrays) and the camera constants.
 uint64_t sceneHash(const hrt_flat_scene& f, const hrt_camera& cam) {
     uint64_t h = 1469598103934665603ull;
@@ -64,7 +66,7 @@ uint64_t sceneHash(const hrt_flat_scene& f, const hrt_camera& cam) {
 
 // what a checkpoint's scene_hash holds: the scene and camera, and whether the render estimates with next-event estimation
 uint64_t renderHash(const hrt_flat_scene& f, const hrt_camera& cam, const RenderOptions& opt) {
-    const uint64_t h = sceneHash(f, cam) ^ (opt.nee && opt.nee_lobes ? kNeeLobesHashSalt : 0);
+    const uint64_t h = sceneHash(f, cam) ^ (opt.nee && opt.nee_lobes ? kNeeLobesHashSalt : 0) ^ (opt.stratified ? kStratifiedHashSalt : 0);
     if (opt.nee && opt.nee_emitters) return h ^ kNeeEmittersHashSalt ^ (opt.nee_env ? kNeeEnvHashSalt : 0);
     if (opt.nee && opt.nee_env) return h ^ kNeeEnvHashSalt;
     return opt.nee ? h ^ kNeeHashSalt : h;
@@ -185,7 +187,8 @@ hrt_status render(int /*nThreads*/, const std::shared_ptr<Texture> background, c
     pr.seed_lo = (uint32_t)opt.seed; pr.seed_hi = (uint32_t)(opt.seed >> 32);
     pr.flags = (opt.stats ? HRT_FLAG_STATS : 0) | (opt.thin_lens ? HRT_FLAG_THIN_LENS : 0) | (opt.progress ? HRT_FLAG_PROGRESS : 0) |
                (opt.nee ? HRT_FLAG_NEE : 0) | (opt.nee && opt.nee_env ? HRT_FLAG_NEE_ENV : 0) |
-               (opt.nee && opt.nee_emitters ? HRT_FLAG_NEE_EMITTERS : 0) | (opt.nee && opt.nee_lobes ? HRT_FLAG_NEE_LOBES : 0);
+               (opt.nee && opt.nee_emitters ? HRT_FLAG_NEE_EMITTERS : 0) | (opt.nee && opt.nee_lobes ? HRT_FLAG_NEE_LOBES : 0) |
+               (opt.stratified ? HRT_FLAG_STRATIFIED : 0);
 
     if (opt.adaptive >= 0.0f) return renderAdaptive(flat, cam, pr, film, opt, stats, render_seconds);
 

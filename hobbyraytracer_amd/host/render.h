@@ -18,6 +18,7 @@ struct RenderOptions {
     bool nee = false;                   // next-event estimation with MIS for the rect and sphere lights (--nee, hrt.h HRT_FLAG_NEE)
     bool nee_env = false;               // ... and environment-map importance sampling (--nee-env, HRT_FLAG_NEE_ENV; needs nee)
     bool nee_emitters = false;          // ... over the emitter table (--nee-emitters, HRT_FLAG_NEE_EMITTERS; needs nee)
+    bool stratified = false;            // the stratified sampler (--stratified, HRT_FLAG_STRATIFIED)
     bool nee_lobes = false;             // ... at rough metal and medium vertices too (--nee-lobes, HRT_FLAG_NEE_LOBES; needs nee)
     bool force_rccl = false;            // gather through an RCCL communicator even with one device (--rccl; tests)
     uint32_t quirks = HRT_QUIRKS_REFERENCE;

@@ -257,12 +257,21 @@ enum {
                                     and free `triangle` prims (whose hit test does not accept their geometric triangle) still emit with
                                     weight 1.  A scene without entries renders exactly as without the flag.  Shadow rays
                                     count in hrt_stats::shadow_rays.  Megakernel: HRT_ERR_UNSUPPORTED. */
-    HRT_FLAG_NEE_LOBES = 1u << 8 /* with HRT_FLAG_NEE (alone: HRT_ERR_INVALID); may be combined with HRT_FLAG_NEE_ENV and HRT_FLAG_NEE_EMITTERS:
+    HRT_FLAG_NEE_LOBES = 1u << 8, /* with HRT_FLAG_NEE (alone: HRT_ERR_INVALID); may be combined with HRT_FLAG_NEE_ENV and HRT_FLAG_NEE_EMITTERS:
                                     the vertices that sample a light are, besides the Lambertian ones, every Metal scatter (a Metal, or a
                                     PBR whose mix chose metal) of roughness >= 1/64 and every Isotropic one (a ConstantMedium hit)
                                     (DESIGN.md 4.8); a bounce from such a vertex gets the matching MIS weight.  Dielectric and UVTest
                                     scatters and smoother metals keep weight 1.  Where the other NEE flags have nothing to sample the flag
                                     changes nothing.  Megakernel: HRT_ERR_UNSUPPORTED. */
+    HRT_FLAG_STRATIFIED = 1u << 9 /* the stratified sampler (off = independent Philox words per sample): the samples 0, 1, 2, ...
+                                    of a pixel take, at every draw site (pixel, bounce, purpose, aux), the points of an Owen-scrambled,
+                                    index-shuffled Sobol' (0,2)-sequence, padded across sites (csrc/hrt_rng.h strat_draw).  It replaces the
+                                    draws of the pixel jitter, the lens, the scatter direction and Fresnel coin, and the light and
+                                    environment samples of the NEE flags; ConstantMedium free paths and ballRand keep Philox.  The sequence
+                                    is indexed by the sample index alone, so the film is the same bits for every tiling, device count,
+                                    batch size and adaptive schedule, as without the flag.  Combines with every flag but
+                                    HRT_FLAG_MEGAKERNEL (HRT_ERR_UNSUPPORTED).  The estimate stays unbiased; the samples of a pixel are no
+                                    longer independent, so hrt_render_adaptive's variance estimate over-states the error of the mean. */
 };
 
 typedef struct hrt_rect { int32_t x0, y0, w, h; } hrt_rect;   /* y0 = row index from the TOP (pIdx / W) */
@@ -456,6 +465,10 @@ hrt_status hrt_closest_hit(hrt_scene* scene, const hrt_params* params, int64_t n
  * check CPU == GPU bit for bit.  op: 0 sin, 1 cos, 2 acos, 3 atan2(x=in, y=in2), 4 log,
  * 5 philox (in = counter words as float bits; out 4 words per input). */
 hrt_status hrt_math_probe(int device, int32_t op, int64_t n, const float* in, const float* in2, float* out);
+
+/* Test entry: HRT_FLAG_STRATIFIED's draw (csrc/hrt_rng.h strat_draw) on the GPU for n keys; seed = hrt_params' seed_lo | seed_hi << 32,
+ * keys[4 i ..] = pixel, sample, bounce, purpose | aux << 8; out[4 i ..] = the draw's words x, y, z, w. */
+hrt_status hrt_sampler_probe(int device, uint64_t seed, int64_t n, const uint32_t* keys, uint32_t* out);
 
 /* HRT_FLAG_NEE_ENV's sampling table of an environment map, built by the same kernels hrt_scene_create runs, on the current
  * device, from host memory: texels = W x H x channels fp32 (channels >= 3; rows from the top, as the HRT_TEX_ENV texture stores them).
