@@ -36,6 +36,8 @@ FLAG_STATS, FLAG_MEGAKERNEL, FLAG_TIMING, FLAG_THIN_LENS, FLAG_PROGRESS, FLAG_NE
 FLAG_NEE_EMITTERS = 128
 FLAG_NEE_LOBES = 256
 FLAG_STRATIFIED = 512
+FLAG_ROULETTE = 1024
+ROULETTE_FIRST_BOUNCE, ROULETTE_Q_FLOOR = 3, 0.05   # what a new scene has (hrt_scene_set_roulette)
 
 
 # ---------------------------------------------------------------- structs (hrt.h)
@@ -137,7 +139,7 @@ HIP_SYMBOLS = ["hrt_device_count", "hrt_scene_create", "hrt_scene_destroy", "hrt
                "hrt_multi_create", "hrt_multi_destroy", "hrt_multi_devices", "hrt_multi_uses_rccl", "hrt_multi_render", "hrt_bvh_build_device", "hrt_bvh_build_sah",
                "hrt_debug_bounds_violations", "hrt_scene_progress", "hrt_multi_progress",
                "hrt_render_stripes_adaptive_device", "hrt_render_stripes_adaptive", "hrt_adaptive_mean_device", "hrt_env_table_build",
-               "hrt_emitter_table_build"]
+               "hrt_emitter_table_build", "hrt_scene_set_roulette", "hrt_multi_set_roulette"]
 HOST_SYMBOLS = ["hrt_host_load_yaml", "hrt_host_free", "hrt_host_flat", "hrt_host_film", "hrt_host_camera", "hrt_host_bvh_depth",
                 "hrt_default_params", "hrt_asset_write_teapot_obj", "hrt_asset_write_bust_obj", "hrt_asset_write_hall_hdr",
                 "hrt_host_write_image", "hrt_host_read_hdr", "hrt_host_read_png", "hrt_host_read_jpeg", "hrt_host_write_hdr", "hrt_host_write_pfm", "hrt_host_read_pfm", "hrt_host_last_error", "hrt_host_set_bvh_builder"]
@@ -193,6 +195,8 @@ _hip.hrt_multi_devices.restype = C.c_int32
 _hip.hrt_multi_uses_rccl.argtypes = [_vp]
 _hip.hrt_multi_uses_rccl.restype = C.c_int32
 _hip.hrt_multi_render.argtypes = [_vp, C.POINTER(Camera), C.POINTER(Params), C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _u8p, C.POINTER(Stats)]
+_hip.hrt_scene_set_roulette.argtypes = [_vp, C.c_int32, C.c_float]
+_hip.hrt_multi_set_roulette.argtypes = [_vp, C.c_int32, C.c_float]
 _hip.hrt_math_probe.argtypes = [C.c_int, C.c_int32, C.c_int64, _fp, _fp, _fp]
 _hip.hrt_sampler_probe.argtypes = [C.c_int, C.c_uint64, C.c_int64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
 _hip.hrt_env_table_build.argtypes = [_fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp]
@@ -244,14 +248,17 @@ def _ptr(a, t=_fp):
 
 # ---------------------------------------------------------------- host side
 def default_params(width, height, samples, quirks=QUIRKS_REFERENCE, seed=0, max_depth=50, stats=False, megakernel=False, timing=False,
-                   thin_lens=False, progress=False, nee=False, nee_env=False, nee_emitters=False, nee_lobes=False, stratified=False):
+                   thin_lens=False, progress=False, nee=False, nee_env=False, nee_emitters=False, nee_lobes=False, stratified=False,
+                   roulette=False):
     """nee: next-event estimation with MIS for the scene's rect and sphere lights (FLAG_NEE).
     nee_env: also importance-sample the environment map (FLAG_NEE_ENV); implies nee.
     nee_emitters: sample every rect, box and mesh emitter, wrapped or not, by an alias table (FLAG_NEE_EMITTERS, DESIGN.md 4.7);
     implies nee.
     nee_lobes: rough metal and medium vertices sample lights too (FLAG_NEE_LOBES); implies nee.
     stratified: the samples of a pixel from Owen-scrambled (0,2)-sequences instead of independent Philox words (FLAG_STRATIFIED,
-    DESIGN.md 4.9); combines with every flag but megakernel."""
+    DESIGN.md 4.9); combines with every flag but megakernel.
+    roulette: Russian roulette path termination (FLAG_ROULETTE) with the scene's parameters (DeviceScene.set_roulette /
+    MultiScene.set_roulette; 3 and 0.05 by default); combines with every flag but megakernel and stats."""
     p = Params()
     _host.hrt_default_params(C.byref(p), width, height, samples)
     p.quirks = quirks
@@ -261,7 +268,7 @@ def default_params(width, height, samples, quirks=QUIRKS_REFERENCE, seed=0, max_
     p.flags = (FLAG_STATS if stats else 0) | (FLAG_MEGAKERNEL if megakernel else 0) | (FLAG_TIMING if timing else 0) | \
               (FLAG_THIN_LENS if thin_lens else 0) | (FLAG_PROGRESS if progress else 0) | (FLAG_NEE if nee or nee_env or nee_emitters or nee_lobes else 0) | \
               (FLAG_NEE_ENV if nee_env else 0) | (FLAG_NEE_EMITTERS if nee_emitters else 0) | (FLAG_NEE_LOBES if nee_lobes else 0) | \
-              (FLAG_STRATIFIED if stratified else 0)
+              (FLAG_STRATIFIED if stratified else 0) | (FLAG_ROULETTE if roulette else 0)
     return p
 
 
@@ -482,6 +489,12 @@ class DeviceScene:
         except Exception:
             pass
 
+    def set_roulette(self, first_bounce=ROULETTE_FIRST_BOUNCE, q_floor=ROULETTE_Q_FLOOR):
+        """FLAG_ROULETTE's parameters for the renders of this scene that follow (hrt_scene_set_roulette): roulette from a path's
+        first_bounce-th scatter on, no survival probability below q_floor.  HrtError (HRT_ERR_INVALID) for first_bounce < 0 or a q_floor
+        outside (0, 1]."""
+        _check(_hip.hrt_scene_set_roulette(self._h, first_bounce, q_floor))
+
     def render_tile(self, cam, params, rect=None):
         """-> (h, w, 3) fp32 linear film tile, Stats."""
         if rect is None:
@@ -629,6 +642,10 @@ class MultiScene:
             self.close()
         except Exception:
             pass
+
+    def set_roulette(self, first_bounce=ROULETTE_FIRST_BOUNCE, q_floor=ROULETTE_Q_FLOOR):
+        """DeviceScene.set_roulette for every device of the session (hrt_multi_set_roulette)."""
+        _check(_hip.hrt_multi_set_roulette(self._h, first_bounce, q_floor))
 
     def progress(self):
         d, t = C.c_uint64(0), C.c_uint64(0)

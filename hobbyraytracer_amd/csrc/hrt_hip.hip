@@ -18,6 +18,7 @@
 //   k_wf_shade<STATS, true, ENV, true> / k_wf_shadow<ENV, true>   the emitter table, HRT_FLAG_NEE_EMITTERS (4.7).
 //   k_wf_shade<STATS, true, ENV, EMIT, true> / k_wf_shadow<ENV, EMIT, true>   light samples at rough metal and medium vertices, HRT_FLAG_NEE_LOBES (4.8).
 //   k_wf_gen_st / k_wf_shade_st / k_wf_shadow_st (the same template arguments)   the stratified sampler, HRT_FLAG_STRATIFIED (4.9): hrt_wf_kernels.h.
+//   k_wf_shade_rr / k_wf_shade_st_rr<false, ...>   Russian roulette, HRT_FLAG_ROULETTE (4.10): hrt_wf_kernels.h, hrt_roulette.h.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>   // types and prototypes only: the library is loaded on demand (rccl_api below)
 #include <dlfcn.h>
@@ -36,6 +37,7 @@
 
 #include "hrt_device.h"
 #include "hrt_pack.h"
+#include "hrt_roulette.h"
 
 using namespace hrt;
 
@@ -1144,10 +1146,12 @@ __device__ HRT_WAVE_FN bool path_shade_lobes(const DScene& sc, const hrt_params&
     return ps.bounce >= pr.max_depth;
 }
 
-template <bool STATS, bool NEE = false, bool ENV = false, bool EMIT = false, bool LOBES = false, bool STRAT = false>
+// RR (HRT_FLAG_ROULETTE): a path that scattered plays hrt_roulette.h's rule before anything is stored for its next segment.
+template <bool STATS, bool NEE = false, bool ENV = false, bool EMIT = false, bool LOBES = false, bool STRAT = false, bool RR = false>
 __device__ HRT_WAVE_FN void wf_shade_task(const DScene& sc, const hrt_params& pr, const RenderMap& map, const WfScene& ws, unsigned n_local, int s0, int round,
                                      const WfBuf& w, unsigned task, unsigned n, unsigned lane, unsigned long long lt, MissQueue& mq,
-                                     PathCounters& pc, unsigned& n_seg, unsigned& n_culled, unsigned& live_out, unsigned& qn_out, unsigned& rn_out) {
+                                     PathCounters& pc, unsigned& n_seg, unsigned& n_culled, unsigned& live_out, unsigned& qn_out, unsigned& rn_out,
+                                     int rr_first = 0, float rr_floor = 1.0f) {
     const int par = round & 1, nxt = par ^ 1;
     const unsigned base = task * w.T;
     unsigned out = base, qpos = base, rcount = 0;
@@ -1204,6 +1208,7 @@ __device__ HRT_WAVE_FN void wf_shade_task(const DScene& sc, const hrt_params& pr
             else if (EMIT) ended = path_shade_nee<STATS, true, STRAT>(sc, pr, w, ctx, ps, wh, pc, round > 0 ? w.N[par][pos].w : -1.0f, nrec);
             else if (NEE) ended = path_shade_nee<STATS, false, STRAT>(sc, pr, w, ctx, ps, wh, pc, round > 0 ? w.N[par][pos].w : -1.0f, nrec);
             else ended = path_shade<STATS, STRAT>(sc, pr, ctx, ps, wh, pc);
+            if (RR && !ended) ended = roulette<STRAT>(ctx, round, rr_first, rr_floor, ps.atten);   // a killed path ends as any other does
             if (ended) w.rad[slot] = make_float4(ps.result.x, ps.result.y, ps.result.z, 0.0f);
             else {
                 alive = true;
@@ -1297,6 +1302,19 @@ __device__ HRT_WAVE_FN void wf_shade_counters(const WfBuf& w, DeviceCounters* co
 #include "hrt_wf_kernels.h"
 #undef HRT_K
 #undef HRT_STRAT
+// ... and HRT_FLAG_ROULETTE's twins of k_wf_shade alone, k_wf_shade_rr / k_wf_shade_st_rr: HRT_RR leaves the other two out
+#define HRT_RR
+#define HRT_K(name) name##_rr
+#define HRT_STRAT false
+#include "hrt_wf_kernels.h"
+#undef HRT_K
+#undef HRT_STRAT
+#define HRT_K(name) name##_st_rr
+#define HRT_STRAT true
+#include "hrt_wf_kernels.h"
+#undef HRT_K
+#undef HRT_STRAT
+#undef HRT_RR
 
 // HRT_FLAG_NEE_ENV's sampling table (hrt_device.h env_*).  One CDF of n float64 weights per block of 256 threads, in a fixed
 // order and without atomics, so that every device builds the same bits: thread t sums the contiguous run [t c, (t + 1) c) of the weights
@@ -1735,6 +1753,9 @@ struct hrt_scene {
     // HRT_FLAG_NEE_EMITTERS: the emitter table (hrt_emitters.h), built at hrt_scene_create; n_emit = 0: no table
     DevBuf emit_rec, emit_shade, emit_alias, emit_base;
     int n_emit = 0;
+    // HRT_FLAG_ROULETTE: the rule's two parameters (hrt_scene_set_roulette), kernel arguments of k_wf_shade_rr / k_wf_shade_st_rr
+    int32_t rr_first = HRT_ROULETTE_FIRST_BOUNCE;
+    float rr_floor = HRT_ROULETTE_Q_FLOOR;
 };
 
 namespace {
@@ -1930,6 +1951,13 @@ int bvh_depth(const hrt_flat_scene* f, const hrt_mesh& m) {
     return deepest;
 }
 
+// HRT_FLAG_ROULETTE's two parameters, judged before the handle they are set on (hrt_scene_set_roulette, hrt_multi_set_roulette)
+hrt_status check_roulette(int32_t first_bounce, float q_floor) {
+    if (first_bounce < 0) return fail(HRT_ERR_INVALID, "roulette: first_bounce must be >= 0");
+    if (!(q_floor > 0.0f && q_floor <= 1.0f)) return fail(HRT_ERR_INVALID, "roulette: q_floor must lie in (0, 1]");
+    return HRT_OK;
+}
+
 hrt_status check_params(const hrt_params* p) {
     if (!p) return fail(HRT_ERR_INVALID, "params is NULL");
     if (p->width < 2 || p->height < 2) return fail(HRT_ERR_INVALID, "film must be at least 2x2 (main.cpp:120-121 divides by W-1, H-1)");
@@ -1946,6 +1974,8 @@ hrt_status check_params(const hrt_params* p) {
     if ((p->flags & HRT_FLAG_NEE_LOBES) && !(p->flags & HRT_FLAG_NEE)) return fail(HRT_ERR_INVALID, "HRT_FLAG_NEE_LOBES needs HRT_FLAG_NEE");
     if ((p->flags & HRT_FLAG_MEGAKERNEL) && (p->flags & HRT_FLAG_NEE)) return fail(HRT_ERR_UNSUPPORTED, "next-event estimation renders on the wavefront pipeline only");
     if ((p->flags & HRT_FLAG_MEGAKERNEL) && (p->flags & HRT_FLAG_STRATIFIED)) return fail(HRT_ERR_UNSUPPORTED, "the stratified sampler renders on the wavefront pipeline only");
+    if ((p->flags & HRT_FLAG_MEGAKERNEL) && (p->flags & HRT_FLAG_ROULETTE)) return fail(HRT_ERR_UNSUPPORTED, "Russian roulette renders on the wavefront pipeline only");
+    if ((p->flags & HRT_FLAG_STATS) && (p->flags & HRT_FLAG_ROULETTE)) return fail(HRT_ERR_UNSUPPORTED, "HRT_FLAG_ROULETTE has no counting kernels (HRT_FLAG_STATS); rays and shadow_rays are counted without them");
     return HRT_OK;
 }
 
@@ -2093,6 +2123,9 @@ hrt_status launch_wavefront(hrt_scene* sc, const hrt_camera* cam, const hrt_para
     const bool lobes = nee && (pr->flags & HRT_FLAG_NEE_LOBES) != 0;
     // HRT_FLAG_STRATIFIED: the k_wf_*_st kernels, whose jitter, lens, scatter, light and environment draws are strat_draw's
     const bool strat = (pr->flags & HRT_FLAG_STRATIFIED) != 0;
+    // HRT_FLAG_ROULETTE: k_wf_shade_rr / k_wf_shade_st_rr, which end paths of low throughput (hrt_roulette.h); check_params
+    // has refused the flag together with HRT_FLAG_STATS, so only their <false, ...> instantiations exist
+    const bool rr = (pr->flags & HRT_FLAG_ROULETTE) != 0;
     size_t cap = wf_max_slots(sc, nee, lobes);
     const int s_end = s_first + s_count;
     int chunk = (int)std::min<size_t>((size_t)s_count, std::max<size_t>(1, cap / n_local));
@@ -2136,6 +2169,7 @@ hrt_status launch_wavefront(hrt_scene* sc, const hrt_camera* cam, const hrt_para
     if (stale_ff) tail_round = D;        // k_wf_tail has no stage for the stale frontFace (k_wf_stale): round by round
     if (nee) tail_round = D;             // ... nor for the light samples (k_wf_shadow)
     if (strat) tail_round = D;           // ... nor the stratified sampler (k_wf_shade_st)
+    if (rr) tail_round = D;              // ... nor roulette (k_wf_shade_rr)
     tail_round = std::min(tail_round, D);
     int leaf_num = 48;                                   // k_wf_ext: start the leaf phase when >= 48/64 of the busy lanes wait at a leaf
     if (const char* e = getenv("HRT_EXT_LEAF_NUM")) leaf_num = atoi(e);
@@ -2238,7 +2272,21 @@ hrt_status launch_wavefront(hrt_scene* sc, const hrt_camera* cam, const hrt_para
             }
             next_counters((unsigned)task_blocks * 4u);
             w.ref_prod = ref_block(r + 1, 0); w.ref_cons = ref_block(D, 0);
-            if (lobes) {
+            if (rr) {
+                auto shade_rr = [&](auto kernel) {
+                    hipLaunchKernelGGL(kernel, dim3(task_blocks), dim3(256), 0, stream, sc->ds, *pr, map, ws, n_local, s0, r, w, sc->d_counters, (int)sc->rr_first, sc->rr_floor);
+                };
+                if (lobes)
+                    with_bool(env, [&](auto E) { with_bool(emit, [&](auto M) {
+                        shade_rr(strat ? k_wf_shade_st_rr<false, true, decltype(E)::value, decltype(M)::value, true> : k_wf_shade_rr<false, true, decltype(E)::value, decltype(M)::value, true>);
+                    }); });
+                else if (emit)
+                    with_bool(env, [&](auto E) { shade_rr(strat ? k_wf_shade_st_rr<false, true, decltype(E)::value, true> : k_wf_shade_rr<false, true, decltype(E)::value, true>); });
+                else if (env)
+                    shade_rr(strat ? k_wf_shade_st_rr<false, true, true> : k_wf_shade_rr<false, true, true>);
+                else
+                    with_bool(nee, [&](auto N) { shade_rr(strat ? k_wf_shade_st_rr<false, decltype(N)::value> : k_wf_shade_rr<false, decltype(N)::value>); });
+            } else if (lobes) {
                 with_bool(env, [&](auto E) { with_bool(emit, [&](auto M) { with_bool(stats, [&](auto S) {
                     hipLaunchKernelGGL((strat ? k_wf_shade_st<decltype(S)::value, true, decltype(E)::value, decltype(M)::value, true> : k_wf_shade<decltype(S)::value, true, decltype(E)::value, decltype(M)::value, true>), dim3(task_blocks), dim3(256), 0, stream, sc->ds, *pr,
                                        map, ws, n_local, s0, r, w, sc->d_counters);
@@ -2588,6 +2636,13 @@ hrt_status hrt_scene_create(const hrt_flat_scene* f, int device, hrt_scene** out
     *out = sc.release();
     return HRT_OK;
     HRT_API_CATCH
+}
+
+hrt_status hrt_scene_set_roulette(hrt_scene* sc, int32_t first_bounce, float q_floor) {
+    HRTCHK(check_roulette(first_bounce, q_floor));
+    if (!sc) return fail(HRT_ERR_INVALID, "scene is NULL");
+    sc->rr_first = first_bounce; sc->rr_floor = q_floor;
+    return HRT_OK;
 }
 
 int32_t hrt_stripe_rows(int32_t height, int32_t R, int32_t rank, int32_t G) {
@@ -3094,6 +3149,13 @@ hrt_status hrt_multi_progress(const hrt_multi* m, uint64_t* done, uint64_t* tota
         if (s && hrt_scene_progress(s, &a, &b) == HRT_OK) { d += a; t += b; }
     }
     *done = d; *total = t;
+    return HRT_OK;
+}
+
+hrt_status hrt_multi_set_roulette(hrt_multi* m, int32_t first_bounce, float q_floor) {
+    HRTCHK(check_roulette(first_bounce, q_floor));
+    if (!m) return fail(HRT_ERR_INVALID, "session is NULL");
+    for (hrt_scene* s : m->scenes) { s->rr_first = first_bounce; s->rr_floor = q_floor; }
     return HRT_OK;
 }
 

@@ -33,8 +33,10 @@ enum rng_purpose : uint32_t {
                       //   x = light choice, y / z = the point on the light, w = the root choice (hrt_device.h nee_*)
                       //   HRT_FLAG_NEE_EMITTERS (hrt_device.h emit_*): aux 0 keeps these words, x = the alias slot
                       //   ((uint64)x n >> 32); aux 1 word x = the alias coin (its y, z, w are unused)
-    RNG_ENV = 7       // HRT_FLAG_NEE_ENV only: per eligible vertex (bounce field = the vertex's bounce) aux = 0: x = row, y = column,
+    RNG_ENV = 7,      // HRT_FLAG_NEE_ENV only: per eligible vertex (bounce field = the vertex's bounce) aux = 0: x = row, y = column,
                       //   z = phi in the cell, w = cos theta in the cell; aux = 1: x = the root choice (hrt_device.h env_*)
+    RNG_ROULETTE = 8  // HRT_FLAG_ROULETTE only: per vertex that plays (bounce field = the vertex's bounce, aux = 0): x = the survival coin
+                      //   (hrt_roulette.h)
 };
 // Final counter layout: (pixel, sample, bounce, purpose | aux << 8).  The path's own draws (JITTER, LENS, SCATTER, BALL, MEDIUM)
 // use bounce = the segment's index; HRT_FLAG_NEE's shadow ray of the vertex at bounce b draws its ConstantMedium free paths
@@ -100,6 +102,7 @@ HRT_HD u32x4 rng_draw(const rng_ctx& c, uint32_t purpose, uint32_t aux) {
 //               RNG_LIGHT aux 1    x = A0: the alias coin
 //               RNG_ENV aux 0      x, y = A0, A1: row, column;  z, w = B0, B1: phi, cos theta in the cell
 //               RNG_ENV aux 1      x = A0: the root choice
+//               RNG_ROULETTE       x = A0: the survival coin (HRT_FLAG_ROULETTE)
 //   not stratified: RNG_MEDIUM (drawn inside the traversal), RNG_BALL (a rejection loop) and RNG_BUILD keep rng_draw.
 #define HRT_RNG_SEEDS 0xFFFFFFFFu
 #define HRT_RNG_SEEDS_BIT 0x80000000u

@@ -7,10 +7,25 @@
 // the text is shared by inclusion, not through a __device__ body both kernels call, because that body, although always inlined, changed
 // the default kernels' code (kernel arguments reached through references: 1 % more instructions in k_wf_shade<false, false>, +0.2 ms on
 // the headline frame).  This way the default kernels are compiled from the statements they always were.
+// HRT_FLAG_ROULETTE includes it twice more, with HRT_RR defined, for k_wf_shade alone:
+//   HRT_K(name) = name##_rr,    HRT_STRAT = false : k_wf_shade_rr, and
+//   HRT_K(name) = name##_st_rr, HRT_STRAT = true  : k_wf_shade_st_rr,
+// which take the rule's two parameters as kernel arguments of their own (hrt_params does not grow) and hand them to wf_shade_task<...,
+// RR = true>.  k_wf_gen and k_wf_shadow play no roulette and are not compiled again.
 #if !defined(HRT_K) || !defined(HRT_STRAT)
 #error "include from hrt_hip.hip with HRT_K and HRT_STRAT defined"
 #endif
+#ifdef HRT_RR
+#define HRT_RR_ON true
+#define HRT_RR_PARAMS , int rr_first, float rr_floor
+#define HRT_RR_ARGS , rr_first, rr_floor
+#else
+#define HRT_RR_ON false
+#define HRT_RR_PARAMS
+#define HRT_RR_ARGS
+#endif
 
+#ifndef HRT_RR
 // Camera rays (main.cpp:115-123) of every slot of the batch + the preparation of their first segment.
 template <bool STATS>
 __global__ __launch_bounds__(256) void HRT_K(k_wf_gen)(DScene sc, hrt_camera cam, hrt_params pr, RenderMap map, WfScene ws, unsigned n_local, int s0,
@@ -50,6 +65,7 @@ __global__ __launch_bounds__(256) void HRT_K(k_wf_gen)(DScene sc, hrt_camera cam
         if (lane == 0 && c) atomicAdd(&counters->box_tests, 2ull * c);   // the root's two boxes were tested
     }
 }
+#endif   // !HRT_RR
 
 // One round's shading of every task (wf_shade_task).
 // ENV (HRT_FLAG_NEE_ENV, with NEE only): the environment map's MIS weight on escapes from eligible vertices
@@ -57,7 +73,7 @@ __global__ __launch_bounds__(256) void HRT_K(k_wf_gen)(DScene sc, hrt_camera cam
 // LOBES (HRT_FLAG_NEE_LOBES, with NEE only): rough Metal and Isotropic vertices are eligible too
 template <bool STATS, bool NEE, bool ENV = false, bool EMIT = false, bool LOBES = false>
 __global__ __launch_bounds__(256, HRT_SHADE_WAVES) void HRT_K(k_wf_shade)(DScene sc, hrt_params pr, RenderMap map, WfScene ws, unsigned n_local, int s0, int round,
-                                                         WfBuf w, DeviceCounters* counters) {
+                                                         WfBuf w, DeviceCounters* counters HRT_RR_PARAMS) {
     const unsigned lane = threadIdx.x & 63u;
     const unsigned wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const unsigned long long lt = (1ull << lane) - 1ull;
@@ -73,13 +89,14 @@ __global__ __launch_bounds__(256, HRT_SHADE_WAVES) void HRT_K(k_wf_shade)(DScene
     PathCounters pc; pc.rays = 0; pc.samples = 0; pc.mesh_hits = 0; pc.env_lookups = 0; pc.bvh.box_tests = 0; pc.bvh.tri_tests = 0;
     HRT_FOR_MY_TASKS(task, w, wave, lane) {
         unsigned live, qn, rn;
-        wf_shade_task<STATS, NEE, ENV, EMIT, LOBES, HRT_STRAT>(sc, pr, map, ws, n_local, s0, round, w, task, HRT_UNIFORM(w.live[task]), lane, lt, mq, pc, n_seg, n_culled, live, qn, rn);
+        wf_shade_task<STATS, NEE, ENV, EMIT, LOBES, HRT_STRAT, HRT_RR_ON>(sc, pr, map, ws, n_local, s0, round, w, task, HRT_UNIFORM(w.live[task]), lane, lt, mq, pc, n_seg, n_culled, live, qn, rn HRT_RR_ARGS);
         if (lane == 0) { w.live[task] = live; w.qn[task] = qn; w.rn[task] = rn; if (rn) wf_ref_publish(w, task, rn); }
     }
     if (mq.count) missq_flush<STATS, ENV>(sc, w, mq, lane, mq.count, pc);
     wf_shade_counters<STATS>(w, counters, wave, lane, n_seg, n_culled, pc);
 }
 
+#ifndef HRT_RR
 // The light samples of one round's survivors (the comment at the place of inclusion in hrt_hip.hip says what they are).  With HRT_STRAT
 // the RNG_LIGHT and RNG_ENV draws are the stratified sampler's; the shadow rays' ConstantMedium draws inside world_hit keep rng_draw.
 template <bool ENV, bool EMIT = false, bool LOBES = false>
@@ -223,3 +240,7 @@ __global__ __launch_bounds__(HRT_BLOCK) void HRT_K(k_wf_shadow)(DScene sc, hrt_p
     const unsigned c = wave_sum(n_shadow);
     if (lane == 0 && c) w.wave_shadow[wave] += (unsigned long long)c;      // this wave's own cell
 }
+#endif   // !HRT_RR
+#undef HRT_RR_ON
+#undef HRT_RR_PARAMS
+#undef HRT_RR_ARGS

@@ -19,6 +19,11 @@
 //     --stratified (the samples of a pixel from Owen-scrambled (0,2)-sequences instead of independent numbers; combines
 //         with every flag above and below.  With --adaptive the samples of a pixel are negatively correlated, so the estimated standard
 //         error over-states the real one: a pixel stops no earlier than it should, and may take more samples than it needs)
+//     --roulette (Russian roulette, DESIGN.md 4.10: from a path's third scatter on it survives with probability q = max(0.05, min(1, its
+//         largest attenuation component)) and survivors are re-weighted by 1 / q; unbiased, fewer segments, slightly more noise per sample;
+//         combines with the --nee flags and --stratified; with it --stats prints its line without box_tests / tri_tests)
+//     --roulette-start N (the scatter from which roulette is played, 3; implies --roulette)
+//     --roulette-floor Q (the smallest survival probability, in (0, 1], 0.05; implies --roulette)
 //     --no-progress (no reporter thread and no progress counter on the device: main.cpp:97-109), --progress-ms N (its interval, 500)
 //     --rccl (gather the film through an RCCL communicator even on one GPU; with --gpus N > 1 it always is)
 //     --adaptive T (adaptive sampling: a pixel stops once the relative standard error of its mean luminance is below T;
@@ -90,6 +95,19 @@ int main(int argc, char** argv) {
         else if (a == "--nee-emitters") { opt.nee = true; opt.nee_emitters = true; }
         else if (a == "--nee-lobes") { opt.nee = true; opt.nee_lobes = true; }
         else if (a == "--stratified") opt.stratified = true;
+        else if (a == "--roulette") opt.roulette = true;
+        else if (a == "--roulette-start") {
+            const char* v = next("--roulette-start");
+            char* end = nullptr;
+            const long n = std::strtol(v, &end, 10);
+            if (end == v || *end != '\0' || n < 0 || n > 0x7fffffffl) { std::cerr << "--roulette-start takes an integer >= 0" << std::endl; return 2; }
+            opt.roulette = true; opt.roulette_start = (int)n;
+        }
+        else if (a == "--roulette-floor") {
+            opt.roulette_floor = number("--roulette-floor", next("--roulette-floor"));
+            if (!(opt.roulette_floor > 0.0f && opt.roulette_floor <= 1.0f)) { std::cerr << "--roulette-floor takes a number in (0, 1]" << std::endl; return 2; }
+            opt.roulette = true;
+        }
         else if (a == "--obj-indices") { std::string v = next("--obj-indices"); setenv("HRT_OBJ_INDICES", v == "rebased" ? "rebased" : "reference", 1); }
         else if (a == "--bvh") {     // who builds the meshes' culling trees: the host (binned SAH, default) or the GPU (gpu-sah: the same tree; lbvh: fastest to build, +16 % box tests)
             const std::string v = next("--bvh");

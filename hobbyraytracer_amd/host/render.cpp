@@ -44,6 +44,9 @@ constexpr uint64_t kNeeEmittersHashSalt = 0x4e45452d454d4954ull;   // "NEE-EMIT"
 constexpr uint64_t kNeeLobesHashSalt = 0x4e45452d4c4f4245ull;   // "NEE-LOBE"
 // ... and one with --stratified its own, whatever the estimator: its sums continue a sequence, not a stream of independent samples
 constexpr uint64_t kStratifiedHashSalt = 0x535452415449464cull;   // "STRATIFL"
+// ... and one with --roulette its own, with the rule's two parameters folded in: survivors are re-weighted by them, so only a render
+// with the same settings continues its sums
+constexpr uint64_t kRouletteHashSalt = 0x524f554c45545445ull;   // "ROULETTE"
 // FNV-1a over everything the kernels read of the scene (hrt_flat_scene's arrays) and the camera constants.
 uint64_t sceneHash(const hrt_flat_scene& f, const hrt_camera& cam) {
     uint64_t h = 1469598103934665603ull;
@@ -66,7 +69,12 @@ uint64_t sceneHash(const hrt_flat_scene& f, const hrt_camera& cam) {
 
 // what a checkpoint's scene_hash holds: the scene and camera, and whether the render estimates with next-event estimation
 uint64_t renderHash(const hrt_flat_scene& f, const hrt_camera& cam, const RenderOptions& opt) {
-    const uint64_t h = sceneHash(f, cam) ^ (opt.nee && opt.nee_lobes ? kNeeLobesHashSalt : 0) ^ (opt.stratified ? kStratifiedHashSalt : 0);
+    uint64_t h = sceneHash(f, cam) ^ (opt.nee && opt.nee_lobes ? kNeeLobesHashSalt : 0) ^ (opt.stratified ? kStratifiedHashSalt : 0);
+    if (opt.roulette) {
+        uint32_t floor_bits;
+        std::memcpy(&floor_bits, &opt.roulette_floor, sizeof(floor_bits));
+        h ^= (kRouletteHashSalt ^ (uint64_t)(uint32_t)opt.roulette_start ^ ((uint64_t)floor_bits << 32)) * 1099511628211ull;
+    }
     if (opt.nee && opt.nee_emitters) return h ^ kNeeEmittersHashSalt ^ (opt.nee_env ? kNeeEnvHashSalt : 0);
     if (opt.nee && opt.nee_env) return h ^ kNeeEnvHashSalt;
     return opt.nee ? h ^ kNeeHashSalt : h;
@@ -116,6 +124,11 @@ hrt_status renderAdaptive(const hrt_flat_scene& flat, const hrt_camera& cam, hrt
     hrt_scene* sc = nullptr;
     hrt_status st = hrt_scene_create(&flat, 0, &sc);
     if (st != HRT_OK) { std::cerr << "hrt_scene_create: " << hrt_status_str(st) << ": " << hrt_last_error() << std::endl; return st; }
+    if (opt.roulette && (st = hrt_scene_set_roulette(sc, opt.roulette_start, opt.roulette_floor)) != HRT_OK) {
+        std::cerr << "hrt_scene_set_roulette: " << hrt_status_str(st) << ": " << hrt_last_error() << std::endl;
+        hrt_scene_destroy(sc);
+        return st;
+    }
     std::vector<float> sums((size_t)numPixels * 3), sq((size_t)numPixels);
     std::vector<int32_t> count((size_t)numPixels, 0);
     std::vector<float>& lin = film->linear();
@@ -185,10 +198,14 @@ hrt_status render(int /*nThreads*/, const std::shared_ptr<Texture> background, c
     pr.width = f.width; pr.height = f.height; pr.samples = f.samples;
     pr.max_depth = opt.max_depth; pr.t_min = 0.001f; pr.quirks = opt.quirks;
     pr.seed_lo = (uint32_t)opt.seed; pr.seed_hi = (uint32_t)(opt.seed >> 32);
-    pr.flags = (opt.stats ? HRT_FLAG_STATS : 0) | (opt.thin_lens ? HRT_FLAG_THIN_LENS : 0) | (opt.progress ? HRT_FLAG_PROGRESS : 0) |
+    // (--roulette has no counting kernels, and the library refuses the two flags together: --stats then prints its line from the
+    //  counters that are always kept, and says so)
+    if (opt.stats && opt.roulette)
+        std::cerr << "--stats with --roulette: box_tests, tri_tests, mesh_hits and env_lookups are not counted (0 in the line); rays, samples and shadow_rays are" << std::endl;
+    pr.flags = (opt.stats && !opt.roulette ? HRT_FLAG_STATS : 0) | (opt.thin_lens ? HRT_FLAG_THIN_LENS : 0) | (opt.progress ? HRT_FLAG_PROGRESS : 0) |
                (opt.nee ? HRT_FLAG_NEE : 0) | (opt.nee && opt.nee_env ? HRT_FLAG_NEE_ENV : 0) |
                (opt.nee && opt.nee_emitters ? HRT_FLAG_NEE_EMITTERS : 0) | (opt.nee && opt.nee_lobes ? HRT_FLAG_NEE_LOBES : 0) |
-               (opt.stratified ? HRT_FLAG_STRATIFIED : 0);
+               (opt.stratified ? HRT_FLAG_STRATIFIED : 0) | (opt.roulette ? HRT_FLAG_ROULETTE : 0);
 
     if (opt.adaptive >= 0.0f) return renderAdaptive(flat, cam, pr, film, opt, stats, render_seconds);
 
@@ -197,6 +214,11 @@ hrt_status render(int /*nThreads*/, const std::shared_ptr<Texture> background, c
     st = hrt_multi_create(&flat, G, nullptr, opt.force_rccl ? 1 : 0, &multi);
     if (st != HRT_OK) {
         std::cerr << "hrt_multi_create(" << G << " devices): " << hrt_status_str(st) << ": " << hrt_last_error() << std::endl;
+        return st;
+    }
+    if (opt.roulette && (st = hrt_multi_set_roulette(multi, opt.roulette_start, opt.roulette_floor)) != HRT_OK) {
+        std::cerr << "hrt_multi_set_roulette: " << hrt_status_str(st) << ": " << hrt_last_error() << std::endl;
+        hrt_multi_destroy(multi);
         return st;
     }
 

@@ -20,6 +20,9 @@ struct RenderOptions {
     bool nee_emitters = false;          // ... over the emitter table (--nee-emitters, HRT_FLAG_NEE_EMITTERS; needs nee)
     bool stratified = false;            // the stratified sampler (--stratified, HRT_FLAG_STRATIFIED)
     bool nee_lobes = false;             // ... at rough metal and medium vertices too (--nee-lobes, HRT_FLAG_NEE_LOBES; needs nee)
+    bool roulette = false;              // Russian roulette (--roulette, HRT_FLAG_ROULETTE) ...
+    int roulette_start = 3;             // ... from a path's N-th scatter on (--roulette-start N)
+    float roulette_floor = 0.05f;       // ... with no survival probability below Q (--roulette-floor Q)
     bool force_rccl = false;            // gather through an RCCL communicator even with one device (--rccl; tests)
     uint32_t quirks = HRT_QUIRKS_REFERENCE;
     uint64_t seed = 0;

@@ -263,7 +263,7 @@ enum {
                                     (DESIGN.md 4.8); a bounce from such a vertex gets the matching MIS weight.  Dielectric and UVTest
                                     scatters and smoother metals keep weight 1.  Where the other NEE flags have nothing to sample the flag
                                     changes nothing.  Megakernel: HRT_ERR_UNSUPPORTED. */
-    HRT_FLAG_STRATIFIED = 1u << 9 /* the stratified sampler (off = independent Philox words per sample): the samples 0, 1, 2, ...
+    HRT_FLAG_STRATIFIED = 1u << 9, /* the stratified sampler (off = independent Philox words per sample): the samples 0, 1, 2, ...
                                     of a pixel take, at every draw site (pixel, bounce, purpose, aux), the points of an Owen-scrambled,
                                     index-shuffled Sobol' (0,2)-sequence, padded across sites (csrc/hrt_rng.h strat_draw).  It replaces the
                                     draws of the pixel jitter, the lens, the scatter direction and Fresnel coin, and the light and
@@ -272,6 +272,15 @@ enum {
                                     batch size and adaptive schedule, as without the flag.  Combines with every flag but
                                     HRT_FLAG_MEGAKERNEL (HRT_ERR_UNSUPPORTED).  The estimate stays unbiased; the samples of a pixel are no
                                     longer independent, so hrt_render_adaptive's variance estimate over-states the error of the mean. */
+    HRT_FLAG_ROULETTE = 1u << 10 /* Russian roulette (off = every path is followed until it escapes, is absorbed or reaches
+                                    max_depth): at every vertex that scatters, from the first_bounce-th scatter of a path on, the path
+                                    survives with probability q = max(q_floor, min(1, the largest component of its attenuation)) and a
+                                    survivor's attenuation is divided by q (csrc/hrt_roulette.h; the parameters: hrt_scene_set_roulette,
+                                    3 and 0.05 by default).  The coin is a draw of its own keyed by (pixel, sample, bounce), so the film is
+                                    the same bits for every tiling, device count, batch size and adaptive schedule.  The estimate stays
+                                    unbiased; hrt_stats::rays and shadow_rays count what was traced, which is less than without the flag.
+                                    Combines with the NEE flags and HRT_FLAG_STRATIFIED; with HRT_FLAG_MEGAKERNEL, and with HRT_FLAG_STATS
+                                    (there are no counting variants of its kernels), every render call returns HRT_ERR_UNSUPPORTED. */
 };
 
 typedef struct hrt_rect { int32_t x0, y0, w, h; } hrt_rect;   /* y0 = row index from the TOP (pIdx / W) */
@@ -328,6 +337,10 @@ hrt_status hrt_device_count(int* n);
 /* Uploads (copies) the flat scene to `device`.  Validates every index. */
 hrt_status hrt_scene_create(const hrt_flat_scene* flat, int device, hrt_scene** out);
 void hrt_scene_destroy(hrt_scene* scene);
+/* HRT_FLAG_ROULETTE's parameters for the renders of `scene` that follow: roulette is played from a path's first_bounce-th scatter on
+ * (0 and 1: from the first) and no path survives with a probability below q_floor.  A new scene has 3 and 0.05.  HRT_ERR_INVALID for
+ * first_bounce < 0 and for a q_floor outside (0, 1] or NaN; the scene then keeps what it had.  Without the flag they are not read. */
+hrt_status hrt_scene_set_roulette(hrt_scene* scene, int32_t first_bounce, float q_floor);
 
 /* Blocking: renders tile (x0,y0,w,h) of the W x H film and writes
  * w*h*3 fp32 LINEAR radiance means (row-major within the tile, row 0 = top)
@@ -428,6 +441,8 @@ hrt_status hrt_multi_create(const hrt_flat_scene* flat, int32_t n_devices, const
 void hrt_multi_destroy(hrt_multi* m);
 int32_t hrt_multi_devices(const hrt_multi* m);
 int32_t hrt_multi_uses_rccl(const hrt_multi* m);
+/* hrt_scene_set_roulette for every device of the session. */
+hrt_status hrt_multi_set_roulette(hrt_multi* m, int32_t first_bounce, float q_floor);
 /* Adds samples [sample_first, sample_first + sample_count) of params->samples on all devices at once (sample_count < 0: all that
  * are left; 0: none, only gather what is there), gathers, and hands out (both optional, caller-owned HOST buffers):
  *   out_sums  W*H*3 floats in film order: the running sums -- the means once the range has reached params->samples
