@@ -139,7 +139,8 @@ HIP_SYMBOLS = ["hrt_device_count", "hrt_scene_create", "hrt_scene_destroy", "hrt
                "hrt_multi_create", "hrt_multi_destroy", "hrt_multi_devices", "hrt_multi_uses_rccl", "hrt_multi_render", "hrt_bvh_build_device", "hrt_bvh_build_sah",
                "hrt_debug_bounds_violations", "hrt_scene_progress", "hrt_multi_progress",
                "hrt_render_stripes_adaptive_device", "hrt_render_stripes_adaptive", "hrt_adaptive_mean_device", "hrt_env_table_build",
-               "hrt_emitter_table_build", "hrt_scene_set_roulette", "hrt_multi_set_roulette"]
+               "hrt_emitter_table_build", "hrt_scene_set_roulette", "hrt_multi_set_roulette",
+               "hrt_render_aov_tile", "hrt_render_aov_stripes_device", "hrt_render_aov_stripes"]
 HOST_SYMBOLS = ["hrt_host_load_yaml", "hrt_host_free", "hrt_host_flat", "hrt_host_film", "hrt_host_camera", "hrt_host_bvh_depth",
                 "hrt_default_params", "hrt_asset_write_teapot_obj", "hrt_asset_write_bust_obj", "hrt_asset_write_hall_hdr",
                 "hrt_host_write_image", "hrt_host_read_hdr", "hrt_host_read_png", "hrt_host_read_jpeg", "hrt_host_write_hdr", "hrt_host_write_pfm", "hrt_host_read_pfm", "hrt_host_last_error", "hrt_host_set_bvh_builder"]
@@ -197,6 +198,9 @@ _hip.hrt_multi_uses_rccl.restype = C.c_int32
 _hip.hrt_multi_render.argtypes = [_vp, C.POINTER(Camera), C.POINTER(Params), C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _u8p, C.POINTER(Stats)]
 _hip.hrt_scene_set_roulette.argtypes = [_vp, C.c_int32, C.c_float]
 _hip.hrt_multi_set_roulette.argtypes = [_vp, C.c_int32, C.c_float]
+_hip.hrt_render_aov_tile.argtypes = [_vp, C.POINTER(Camera), C.POINTER(Params), Rect, _fp]
+_hip.hrt_render_aov_stripes_device.argtypes = [_vp, C.POINTER(Camera), C.POINTER(Params), C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32, _vp]
+_hip.hrt_render_aov_stripes.argtypes = [_vp, C.POINTER(Camera), C.POINTER(Params), C.c_int32, C.c_int32, C.c_int32, _fp, C.c_int32, C.c_int32]
 _hip.hrt_math_probe.argtypes = [C.c_int, C.c_int32, C.c_int64, _fp, _fp, _fp]
 _hip.hrt_sampler_probe.argtypes = [C.c_int, C.c_uint64, C.c_int64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
 _hip.hrt_env_table_build.argtypes = [_fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp]
@@ -467,6 +471,14 @@ def stripe_row_indices(height, rows_per_block, rank, n_ranks):
     return np.array([_hip.hrt_stripe_row_index(height, rows_per_block, rank, n_ranks, i) for i in range(n)], dtype=np.int64)
 
 
+def split_aov(buf):
+    """A raw feature buffer [..., 8] (hrt_render_aov_*: albedo r g b, alpha, normal x y z, depth per pixel) as a dict of views:
+    albedo [..., 3], alpha [...], normal [..., 3], depth [...]."""
+    if buf.shape[-1] != 8:
+        raise ValueError("a feature buffer has 8 floats per pixel")
+    return {"albedo": buf[..., 0:3], "alpha": buf[..., 3], "normal": buf[..., 4:7], "depth": buf[..., 7]}
+
+
 class DeviceScene:
     """hrt_scene: the flat scene resident on one GPU."""
 
@@ -594,6 +606,36 @@ class DeviceScene:
         with np.errstate(divide="ignore", invalid="ignore"):
             mean = sums / count.astype(np.float32)[..., None]
         return mean, count, total
+
+    def render_aov_tile(self, cam, params, rect=None):
+        """The feature buffers of a film tile (hrt_render_aov_tile), means over samples [0, params.samples) -> a dict of
+        fp32 arrays: albedo [h, w, 3], alpha [h, w], normal [h, w, 3], depth [h, w] (split_aov)."""
+        if rect is None:
+            rect = Rect(0, 0, params.width, params.height)
+        elif not isinstance(rect, Rect):
+            rect = Rect(*rect)
+        out = np.empty((max(rect.h, 0), max(rect.w, 0), 8), dtype=np.float32)
+        _check(_hip.hrt_render_aov_tile(self._h, C.byref(cam), C.byref(params), rect, _ptr(out)))
+        return split_aov(out)
+
+    def render_aov_stripes(self, cam, params, rows_per_block, rank, n_ranks, buf=None, sample_first=0, sample_count=-1):
+        """Adds samples [sample_first, sample_first + sample_count) (-1: all that are left) to the raw feature buffer `buf`
+        ([rows, W, 8] fp32, stripe layout; allocated when not given, which only a call with sample_first == 0 may ask for) and returns it (hrt_render_aov_stripes): running sums, divided by
+        params.samples by the call that reaches it."""
+        rows = stripe_rows(params.height, rows_per_block, rank, n_ranks)
+        if buf is None:
+            if sample_first > 0:
+                raise ValueError("sample_first > 0 continues an accumulation: pass the buffer of the calls before")
+            buf = np.empty((rows, params.width, 8), dtype=np.float32)
+        assert buf.dtype == np.float32 and buf.flags["C_CONTIGUOUS"] and buf.size == rows * params.width * 8
+        _check(_hip.hrt_render_aov_stripes(self._h, C.byref(cam), C.byref(params), rows_per_block, rank, n_ranks, _ptr(buf), sample_first,
+                                           sample_count))
+        return buf
+
+    def render_aov_stripes_device(self, cam, params, rows_per_block, rank, n_ranks, d_buf_ptr, sample_first=0, sample_count=-1, stream=0):
+        """Asynchronous: d_buf_ptr is a device pointer to rows x W x 8 floats (e.g. a torch tensor's .data_ptr())."""
+        _check(_hip.hrt_render_aov_stripes_device(self._h, C.byref(cam), C.byref(params), rows_per_block, rank, n_ranks, _vp(d_buf_ptr),
+                                                  sample_first, sample_count, _vp(stream)))
 
     def stats(self):
         st = Stats()

@@ -19,6 +19,7 @@
 //   k_wf_shade<STATS, true, ENV, EMIT, true> / k_wf_shadow<ENV, EMIT, true>   light samples at rough metal and medium vertices, HRT_FLAG_NEE_LOBES (4.8).
 //   k_wf_gen_st / k_wf_shade_st / k_wf_shadow_st (the same template arguments)   the stratified sampler, HRT_FLAG_STRATIFIED (4.9): hrt_wf_kernels.h.
 //   k_wf_shade_rr / k_wf_shade_st_rr<false, ...>   Russian roulette, HRT_FLAG_ROULETTE (4.10): hrt_wf_kernels.h, hrt_roulette.h.
+//   k_aov<STRAT>        feature buffers: first-hit albedo, alpha, normal and depth of the camera rays (4.11): hrt_aov.h.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>   // types and prototypes only: the library is loaded on demand (rccl_api below)
 #include <dlfcn.h>
@@ -38,6 +39,7 @@
 #include "hrt_device.h"
 #include "hrt_pack.h"
 #include "hrt_roulette.h"
+#include "hrt_aov.h"
 
 using namespace hrt;
 
@@ -1315,6 +1317,52 @@ __device__ HRT_WAVE_FN void wf_shade_counters(const WfBuf& w, DeviceCounters* co
 #undef HRT_K
 #undef HRT_STRAT
 #undef HRT_RR
+
+// Feature buffers (hrt_render_aov_*): first-hit albedo + alpha and normal + depth of the beauty path's camera rays, the
+// per-sample rule of hrt_aov.h.  One thread owns local pixel lp of `map` (slot_pixel: the beauty's tiles and stripes) and walks samples
+// [s0, s0 + n_s) in ascending order, sum = sum + value in fp32 from +0 -- or from the two float4 already in out[2 lp ..] when s0 > 0 --,
+// so neighbouring lanes trace neighbouring pixels' rays; when the range ends at pr.samples the sums are divided by (float)pr.samples,
+// one IEEE division per channel.  Two 16-byte stores per pixel, no atomics, no counters.  STRAT: path_begin's sampler
+// (HRT_FLAG_STRATIFIED); HRT_FLAG_THIN_LENS and pr.quirks are read where path_begin and world_hit read them; no other flag is.
+// Residency: 32 KB of stack + 12 KB of tables per block let three blocks share a CU's 160 KB of LDS, i.e. three waves per SIMD, and
+// the register allocator is given exactly that (<= 168 VGPRs): asking for more waves would buy nothing the LDS admits.
+#define HRT_AOV_WAVES 3
+template <bool STRAT>
+__global__ __launch_bounds__(HRT_BLOCK, HRT_AOV_WAVES) void k_aov(DScene sc, hrt_camera cam, hrt_params pr, RenderMap map, unsigned n_local, int s0, int n_s,
+                                                                  float4* __restrict__ out) {
+    __shared__ int s_stack[HRT_STACK_DEPTH * HRT_BLOCK];
+    __shared__ __attribute__((aligned(16))) uint32_t s_tables[HRT_TABLE_LDS_BYTES / 4];
+    int* stack = s_stack + threadIdx.x;
+    stage_tables(sc, s_tables);
+    const unsigned lp = blockIdx.x * blockDim.x + threadIdx.x;
+    if (lp >= n_local) return;
+    // the stale frontFace of a wrapper-less mesh under Q-3 (WorldHit, hit_record) is not tracked: hit_record's first pass only ever
+    // yields rec.frontFace, which Dielectric::scatter alone reads -- t, p, normal, u, v and the material come from the second pass,
+    // and no field written here depends on the flag
+    sc.stale_ff = 0;
+    int px, py;
+    slot_pixel(map, lp, px, py);
+    float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = a;
+    if (s0 > 0) { a = out[2ull * lp]; b = out[2ull * lp + 1]; }
+    rng_ctx ctx; ctx.seed_lo = pr.seed_lo; ctx.seed_hi = pr.seed_hi; ctx.pixel = (uint32_t)(py * pr.width + px);
+    for (int s = s0; s < s0 + n_s; ++s) {
+        ctx.sample = (uint32_t)s; ctx.bounce = 0;
+        PathState ps;
+        path_begin<STRAT>(cam, pr, px, py, ctx, ps);
+        DCounters cnt; cnt.box_tests = 0; cnt.tri_tests = 0;
+        const WorldHit wh = world_hit<false>(sc, ps.o, ps.d, pr.t_min, __builtin_huge_valf(), pr.quirks, ctx, stack, cnt);
+        const AovSample v = aov_sample(sc, pr, ps.o, ps.d, wh);
+        a = make_float4(a.x + v.A.x, a.y + v.A.y, a.z + v.A.z, a.w + v.A.w);
+        b = make_float4(b.x + v.B.x, b.y + v.B.y, b.z + v.B.z, b.w + v.B.w);
+    }
+    if (s0 + n_s == pr.samples) {
+        const float n = (float)pr.samples;
+        a = make_float4(a.x / n, a.y / n, a.z / n, a.w / n);
+        b = make_float4(b.x / n, b.y / n, b.z / n, b.w / n);
+    }
+    out[2ull * lp] = a;
+    out[2ull * lp + 1] = b;
+}
 
 // HRT_FLAG_NEE_ENV's sampling table (hrt_device.h env_*).  One CDF of n float64 weights per block of 256 threads, in a fixed
 // order and without atomics, so that every device builds the same bits: thread t sums the contiguous run [t c, (t + 1) c) of the weights
@@ -2846,6 +2894,74 @@ hrt_status hrt_render_stripes(hrt_scene* sc, const hrt_camera* cam, const hrt_pa
     return render_via_host(sc, stats, {{out, bytes}}, false, "film stripes", [&](void* const* d, bool&) {
         return hrt_render_stripes_device(sc, cam, pr, R, rank, G, (float*)d[0], nullptr);
     });
+    HRT_API_CATCH
+}
+
+// ---- feature buffers ----
+namespace {
+// the arguments the three hrt_render_aov_* entry points share; *first / *count come back as the range to render
+hrt_status check_aov(hrt_scene* sc, const hrt_camera* cam, const hrt_params* pr, const float* out, int32_t* first, int32_t* count) {
+    if (!sc || !cam || !pr || !out) return fail(HRT_ERR_INVALID, "NULL argument");
+    hrt_params q = *pr;
+    q.flags &= HRT_FLAG_THIN_LENS | HRT_FLAG_STRATIFIED;     // the other flags are not read: no combination of them is refused
+    HRTCHK(check_params(&q));
+    if (*count < 0) *count = pr->samples - *first;
+    if (*first < 0 || *count < 1 || *first > pr->samples - *count) return fail(HRT_ERR_INVALID, "sample range outside [0, samples)");
+    return HRT_OK;
+}
+hrt_status launch_aov(hrt_scene* sc, const hrt_camera* cam, const hrt_params* pr, const RenderMap& map, float* d_out, int32_t first, int32_t count,
+                      hipStream_t stream) {
+    const unsigned n_local = map_pixels(map);
+    if (n_local == 0) return HRT_OK;
+    if ((uintptr_t)d_out & 15u) return fail(HRT_ERR_INVALID, "feature buffer must be 16-byte aligned");
+    const unsigned blocks = (n_local + HRT_BLOCK - 1) / HRT_BLOCK;
+    with_bool(pr->flags & HRT_FLAG_STRATIFIED, [&](auto S) {
+        hipLaunchKernelGGL(k_aov<decltype(S)::value>, dim3(blocks), dim3(HRT_BLOCK), 0, stream, sc->ds, *cam, *pr, map, n_local, (int)first, (int)count, (float4*)d_out);
+    });
+    HIPCHK(hipGetLastError());
+    return HRT_OK;
+}
+// the host-buffer forms: `out` staged in device memory (copied in when the call continues an accumulation), the pass, the copy back.
+// Not render_via_host: the pass counts nothing, and the scene's counters and times stay what the beauty renders left.
+hrt_status aov_via_host(hrt_scene* sc, const hrt_camera* cam, const hrt_params* pr, const RenderMap& map, float* out, int32_t first, int32_t count) {
+    const size_t bytes = (size_t)map_pixels(map) * 8 * sizeof(float);
+    if (!bytes) return HRT_OK;
+    HIPCHK(hipSetDevice(sc->device));
+    DevBuf buf;
+    HRTCHK(buf.alloc(bytes, "hipMalloc(feature buffers)"));
+    if (first > 0) HIPCHK(hipMemcpy(buf.get(), out, bytes, hipMemcpyHostToDevice));
+    HRTCHK(launch_aov(sc, cam, pr, map, buf.get<float>(), first, count, nullptr));
+    HIPCHK(hipMemcpy(out, buf.get(), bytes, hipMemcpyDeviceToHost));
+    return HRT_OK;
+}
+}  // namespace
+
+hrt_status hrt_render_aov_tile(hrt_scene* sc, const hrt_camera* cam, const hrt_params* pr, hrt_rect tile, float* out) {
+    HRT_API_TRY
+    int32_t first = 0, count = -1;
+    HRTCHK(check_aov(sc, cam, pr, out, &first, &count));
+    if (tile.w <= 0 || tile.h <= 0 || tile.x0 < 0 || tile.y0 < 0 || tile.x0 > pr->width - tile.w || tile.y0 > pr->height - tile.h)
+        return fail(HRT_ERR_INVALID, "tile outside the film");
+    return aov_via_host(sc, cam, pr, rect_map(tile), out, first, count);
+    HRT_API_CATCH
+}
+
+hrt_status hrt_render_aov_stripes_device(hrt_scene* sc, const hrt_camera* cam, const hrt_params* pr, int32_t R, int32_t rank, int32_t G,
+                                         float* d_out, int32_t sample_first, int32_t sample_count, void* stream) {
+    HRT_API_TRY
+    HRTCHK(check_aov(sc, cam, pr, d_out, &sample_first, &sample_count));
+    HRTCHK(check_stripes(R, rank, G));
+    HIPCHK(hipSetDevice(sc->device));
+    return launch_aov(sc, cam, pr, stripe_map(pr->width, pr->height, R, rank, G), d_out, sample_first, sample_count, (hipStream_t)stream);
+    HRT_API_CATCH
+}
+
+hrt_status hrt_render_aov_stripes(hrt_scene* sc, const hrt_camera* cam, const hrt_params* pr, int32_t R, int32_t rank, int32_t G,
+                                  float* out, int32_t sample_first, int32_t sample_count) {
+    HRT_API_TRY
+    HRTCHK(check_aov(sc, cam, pr, out, &sample_first, &sample_count));
+    HRTCHK(check_stripes(R, rank, G));
+    return aov_via_host(sc, cam, pr, stripe_map(pr->width, pr->height, R, rank, G), out, sample_first, sample_count);
     HRT_API_CATCH
 }
 

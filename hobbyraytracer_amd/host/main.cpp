@@ -30,6 +30,11 @@
 //         one GPU, no --checkpoint / --resume)   --min-samples N (what every pixel takes first, 16)   --progressive N (the
 //         samples a pass adds to the pixels still active, 16)   --adaptive-floor F (luminance floor of the relative error, 0.01)
 //     --sample-map FILE.pfm (with --adaptive: the samples each pixel took, as floats in all three channels)
+//     --aov PREFIX (feature buffers, DESIGN.md 4.11: PREFIX.albedo.pfm, PREFIX.normal.pfm, PREFIX.depth.pfm and PREFIX.alpha.pfm, the
+//         first-hit albedo, normal, depth and coverage of the film's camera rays, for a denoiser or a compositor; depth and alpha in all
+//         three channels.  First device only; depends on --lens, --stratified, --quirks, --seed and --size, on nothing else)
+//     --aov-spp N (the samples per pixel of that pass, samples 0 .. N - 1; min(spp, 16) by default; 1 <= N <= spp; needs --aov)
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -61,7 +66,9 @@ static void printElapsed(const char* what, std::chrono::high_resolution_clock::t
 int main(int argc, char** argv) {
     auto start = std::chrono::high_resolution_clock::now();
     std::string file = "teapot_scene.yaml";  // main.cpp:146
-    std::string assets, out, makeAssets, dumpLinear, sampleMap;
+    std::string assets, out, makeAssets, dumpLinear, sampleMap, aovPrefix;
+    long aovSpp = -1;
+    bool haveAovSpp = false;
     RenderOptions opt;
     int spp = -1, sw = -1, sh = -1;
     bool haveFile = false;
@@ -125,6 +132,14 @@ int main(int argc, char** argv) {
         else if (a == "--adaptive-floor") opt.adaptive_floor = number("--adaptive-floor", next("--adaptive-floor"));
         else if (a == "--min-samples") opt.min_samples = std::atoi(next("--min-samples"));
         else if (a == "--sample-map") sampleMap = next("--sample-map");
+        else if (a == "--aov") aovPrefix = next("--aov");
+        else if (a == "--aov-spp") {
+            const char* v = next("--aov-spp");
+            char* end = nullptr;
+            aovSpp = std::strtol(v, &end, 10);
+            if (end == v || *end != '\0' || aovSpp < 1 || aovSpp > 0x7fffffffl) { std::cerr << "--aov-spp takes an integer >= 1" << std::endl; return 2; }
+            haveAovSpp = true;
+        }
         else if (!haveFile) { file = a; haveFile = true; }
     }
     if (opt.adaptive >= 0.0f) {
@@ -133,6 +148,7 @@ int main(int argc, char** argv) {
         if (opt.min_samples < 2) { std::cerr << "--min-samples must be >= 2" << std::endl; return 2; }
         if (opt.pass_samples <= 0) opt.pass_samples = 16;
     } else if (!sampleMap.empty()) { std::cerr << "--sample-map needs --adaptive" << std::endl; return 2; }
+    if (haveAovSpp && aovPrefix.empty()) { std::cerr << "--aov-spp needs --aov PREFIX" << std::endl; return 2; }
     if (!makeAssets.empty()) {
         long t = writeTeapotObj(makeAssets + "/teapot.obj", 1.0);
         long b = writeBustObj(makeAssets + "/marble_bust_01.obj", 1.0);
@@ -160,6 +176,14 @@ int main(int argc, char** argv) {
 
     if (opt.resume && opt.checkpoint.empty()) { std::cerr << "--resume needs --checkpoint FILE" << std::endl; return 2; }
     if (opt.adaptive >= 0.0f && film->getFilm().samples < 2) { std::cerr << "--adaptive needs at least 2 samples per pixel" << std::endl; return 2; }
+    if (haveAovSpp && aovSpp > film->getFilm().samples) { std::cerr << "--aov-spp must not exceed the samples per pixel (" << film->getFilm().samples << ")" << std::endl; return 2; }
+    std::vector<float> aov;
+    double aov_s = 0.0;
+    if (!aovPrefix.empty()) {
+        opt.aov_samples = haveAovSpp ? (int)aovSpp : std::min(film->getFilm().samples, 16);
+        opt.aov_out = &aov;
+        opt.aov_seconds = &aov_s;
+    }
     std::vector<int32_t> counts;
     if (opt.adaptive >= 0.0f) opt.sample_counts = &counts;
     if (opt.pass_samples > 0) opt.on_pass = [&film](int) { film->outputFilm(); };   // preview image after every pass
@@ -172,6 +196,18 @@ int main(int argc, char** argv) {
     if (!dumpLinear.empty() && !writePFM(dumpLinear, film->linear().data(), film->getFilm().width, film->getFilm().height)) {
         std::cerr << "cannot write " << dumpLinear << std::endl;
         return -1;
+    }
+    if (!aovPrefix.empty()) {   // the four feature images, through the film's own PFM writer; the scalars in all three channels
+        const int w = film->getFilm().width, h = film->getFilm().height;
+        const size_t n = (size_t)w * h;
+        std::vector<float> img(n * 3);
+        const struct { const char* name; int first; bool scalar; } parts[4] = {{"albedo", 0, false}, {"normal", 4, false}, {"depth", 7, true}, {"alpha", 3, true}};
+        for (const auto& part : parts) {
+            for (size_t i = 0; i < n; ++i)
+                for (int k = 0; k < 3; ++k) img[3 * i + k] = aov[8 * i + part.first + (part.scalar ? 0 : k)];
+            const std::string path = aovPrefix + "." + part.name + ".pfm";
+            if (!writePFM(path, img.data(), w, h)) { std::cerr << "cannot write " << path << std::endl; return -1; }
+        }
     }
     if (!sampleMap.empty()) {
         std::vector<float> m(counts.size() * 3);
@@ -196,6 +232,10 @@ int main(int argc, char** argv) {
         if (opt.nee) {                // the shadow rays of next-event estimation (not part of `rays`)
             const size_t k = std::strlen(extra);
             std::snprintf(extra + k, sizeof(extra) - k, ", \"shadow_rays\": %llu", (unsigned long long)stats.shadow_rays);
+        }
+        if (!aovPrefix.empty()) {     // the feature-buffer pass: its samples per pixel and the wall time of the call
+            const size_t k = std::strlen(extra);
+            std::snprintf(extra + k, sizeof(extra) - k, ", \"aov_spp\": %d, \"aov_s\": %.6f", opt.aov_samples, aov_s);
         }
         std::printf("{\"rays\": %llu, \"samples\": %llu, \"box_tests\": %llu, \"tri_tests\": %llu, \"render_s\": %.6f, "
                     "\"kernel_ms\": %.3f, \"mrays_per_s\": %.3f, \"msamples_per_s\": %.3f, \"algorithmic_gb_per_s\": %.3f, "

@@ -168,6 +168,24 @@ hrt_status renderAdaptive(const hrt_flat_scene& flat, const hrt_camera& cam, hrt
     if (stats) *stats = total;
     return st;
 }
+// The feature-buffer pass (hrt.h hrt_render_aov_tile) on the first device: a scene of its own, gone again before the film's render
+// takes its memory.  Its params are the film's with samples = opt.aov_samples; of the flags only the lens and the sampler are read.
+// The film's session (hrt_multi) does not hand out its scenes, so the pass uploads the scene a second time: *opt.aov_seconds is the
+// wall time of all of it -- upload, pass and release --, none of which is inside render_seconds.
+hrt_status renderAov(const hrt_flat_scene& flat, const hrt_camera& cam, hrt_params pr, const RenderOptions& opt) {
+    pr.samples = opt.aov_samples;
+    pr.flags &= HRT_FLAG_THIN_LENS | HRT_FLAG_STRATIFIED;
+    opt.aov_out->assign((size_t)pr.width * pr.height * 8, 0.0f);
+    const auto t0 = std::chrono::high_resolution_clock::now();
+    hrt_scene* sc = nullptr;
+    hrt_status st = hrt_scene_create(&flat, 0, &sc);
+    if (st != HRT_OK) { std::cerr << "hrt_scene_create: " << hrt_status_str(st) << ": " << hrt_last_error() << std::endl; return st; }
+    st = hrt_render_aov_tile(sc, &cam, &pr, hrt_rect{0, 0, pr.width, pr.height}, opt.aov_out->data());
+    if (st != HRT_OK) std::cerr << "feature buffers: " << hrt_status_str(st) << ": " << hrt_last_error() << std::endl;
+    hrt_scene_destroy(sc);
+    if (opt.aov_seconds) *opt.aov_seconds = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
+    return st;
+}
 }  // namespace
 
 hrt_status render(int /*nThreads*/, const std::shared_ptr<Texture> background, const std::shared_ptr<Hittable> world,
@@ -206,6 +224,8 @@ hrt_status render(int /*nThreads*/, const std::shared_ptr<Texture> background, c
                (opt.nee ? HRT_FLAG_NEE : 0) | (opt.nee && opt.nee_env ? HRT_FLAG_NEE_ENV : 0) |
                (opt.nee && opt.nee_emitters ? HRT_FLAG_NEE_EMITTERS : 0) | (opt.nee && opt.nee_lobes ? HRT_FLAG_NEE_LOBES : 0) |
                (opt.stratified ? HRT_FLAG_STRATIFIED : 0) | (opt.roulette ? HRT_FLAG_ROULETTE : 0);
+
+    if (opt.aov_samples > 0 && opt.aov_out && (st = renderAov(flat, cam, pr, opt)) != HRT_OK) return st;
 
     if (opt.adaptive >= 0.0f) return renderAdaptive(flat, cam, pr, film, opt, stats, render_seconds);
 

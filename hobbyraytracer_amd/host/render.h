@@ -47,6 +47,13 @@ struct RenderOptions {
     int min_samples = 16;
     float adaptive_floor = 0.01f;       // luminance floor of the relative error's denominator (dark pixels)
     std::vector<int32_t>* sample_counts = nullptr;
+    // Feature buffers (--aov, hrt.h hrt_render_aov_tile): aov_samples > 0 runs the pass over samples [0, aov_samples)
+    // of every pixel on the first device, whatever `gpus` is, before the film's render and independent of it (of the estimator, the
+    // batching, a resume, adaptive sampling); *aov_out gets width * height * 8 floats in film order, *aov_seconds (optional) the
+    // wall time of the pass, the upload and release of its own copy of the scene included.  Checkpoints do not hold them.
+    int aov_samples = 0;
+    std::vector<float>* aov_out = nullptr;
+    double* aov_seconds = nullptr;
 };
 
 // render() of main.cpp:81-140.  nThreads is accepted and unused, exactly as in

@@ -423,6 +423,38 @@ int32_t hrt_stripe_rows(int32_t height, int32_t rows_per_block, int32_t rank, in
 /* Absolute row index of local row `local` of rank's stripes; -1 if out of range. */
 int32_t hrt_stripe_row_index(int32_t height, int32_t rows_per_block, int32_t rank, int32_t n_ranks, int32_t local);
 
+/* ---- feature buffers -------------------------------------
+ * What a denoiser or a compositor takes beside the film: first-hit albedo, alpha, normal and depth.  Sample s of pixel (px, py) traces
+ * the camera ray of the film's own path -- the same jitter and lens draw, keyed by (seed, pixel, sample), under HRT_FLAG_THIN_LENS,
+ * HRT_FLAG_STRATIFIED and params->quirks -- once, to its first hit under that key, so a ConstantMedium is met where the film's path
+ * meets it.  Every other flag is accepted and has no effect.  Eight floats per pixel, two groups of four:
+ *   albedo r, g, b   hit: the material's albedo at the hit, i.e. what its scatter multiplies the path by, un-clamped (Lambertian, Metal,
+ *                    Isotropic, PBR; UVTest: the normal, its attenuation); Dielectric: 1, 1, 1; DiffuseLight: emit x strength, each
+ *                    channel clamped to [0, 1], NaN -> 0.            miss: the background's value for the ray, clamped the same way
+ *   alpha            hit: 1                                          miss: 0
+ *   normal x, y, z   hit: hitRecord::normal as the film's path sees it (not re-normalised, not flipped again); 0, 0, 0 for a
+ *                    ConstantMedium.                                 miss: 0, 0, 0
+ *   depth            hit: hitRecord::t x length(direction), fp32     miss: 0
+ * No specular follow-through: a mirror or a glass reports itself.  A pixel holds the plain mean over its samples, misses included
+ * (depth / alpha is the un-premultiplied depth), accumulated as hrt_render_stripes_accumulate_device does it: one thread walks the
+ * pixel's samples in ascending order, sum = sum + value in fp32.  The pass counts nothing: hrt_stats and hrt_scene_stats do not see it.
+ *
+ * Blocking: tile (x0,y0,w,h) of the film, samples [0, params->samples), into the caller-owned HOST buffer of w*h*8 floats (row-major
+ * within the tile, row 0 = top).  HRT_ERR_INVALID for a NULL argument and for an empty tile or one outside the film; the buffer is
+ * then untouched. */
+hrt_status hrt_render_aov_tile(hrt_scene* scene, const hrt_camera* cam, const hrt_params* params, hrt_rect tile, float* out);
+/* Asynchronous, on HIP stream `stream`: the row blocks of `rank` (hrt_render_stripes_device's layout) into a DEVICE buffer of
+ * hrt_stripe_rows(...) * W * 8 floats, 16-byte aligned.  Adds samples [sample_first, sample_first + sample_count) of params->samples to
+ * the buffer: it holds the running SUM of the samples' values, added in sample order.  sample_first == 0 starts a new accumulation (the
+ * buffer need not be cleared).  The call whose range reaches params->samples divides the sums by params->samples, after which the
+ * buffer is bit-identical to a one-shot call with the same params, however the samples were batched.  sample_count < 0 means "all that
+ * are left" (params->samples - sample_first); a range outside [0, params->samples) or an empty one is HRT_ERR_INVALID. */
+hrt_status hrt_render_aov_stripes_device(hrt_scene* scene, const hrt_camera* cam, const hrt_params* params, int32_t rows_per_block,
+                                         int32_t rank, int32_t n_ranks, float* d_out, int32_t sample_first, int32_t sample_count, void* stream);
+/* Blocking host-buffer form: `out` is uploaded first when sample_first > 0, and downloaded after the pass. */
+hrt_status hrt_render_aov_stripes(hrt_scene* scene, const hrt_camera* cam, const hrt_params* params, int32_t rows_per_block, int32_t rank,
+                                  int32_t n_ranks, float* out, int32_t sample_first, int32_t sample_count);
+
 /* ---- multi-GPU session -----------------------------------
  * The reference's render() (main.cpp:81-140) has one parallel loop over all pixels of the film (main.cpp:111-135, no state
  * shared between pixels).  Here the flattened scene is replicated on `n_devices` GPUs of THIS process (`devices` = their
