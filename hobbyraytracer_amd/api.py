@@ -124,6 +124,12 @@ class Adaptive(C.Structure):
     _fields_ = [("min_samples", C.c_int32), ("pass_samples", C.c_int32), ("threshold", C.c_float), ("floor", C.c_float)]
 
 
+class DenoiseParams(C.Structure):
+    """hrt_denoise_params: the guided denoiser's settings (include/hrt.h); denoise_defaults() fills them in."""
+    _fields_ = [("iterations", C.c_int32), ("normal_squarings", C.c_int32), ("sigma_l", C.c_float), ("sigma_z", C.c_float),
+                ("albedo_floor", C.c_float)]
+
+
 class Hit(C.Structure):
     _fields_ = [("t", C.c_float), ("prim", C.c_int32), ("tri", C.c_int32), ("front_face", C.c_int32), ("p", C.c_float * 3),
                 ("normal", C.c_float * 3), ("u", C.c_float), ("v", C.c_float)]
@@ -140,7 +146,8 @@ HIP_SYMBOLS = ["hrt_device_count", "hrt_scene_create", "hrt_scene_destroy", "hrt
                "hrt_debug_bounds_violations", "hrt_scene_progress", "hrt_multi_progress",
                "hrt_render_stripes_adaptive_device", "hrt_render_stripes_adaptive", "hrt_adaptive_mean_device", "hrt_env_table_build",
                "hrt_emitter_table_build", "hrt_scene_set_roulette", "hrt_multi_set_roulette",
-               "hrt_render_aov_tile", "hrt_render_aov_stripes_device", "hrt_render_aov_stripes"]
+               "hrt_render_aov_tile", "hrt_render_aov_stripes_device", "hrt_render_aov_stripes",
+               "hrt_denoise_defaults", "hrt_denoise_workspace_bytes", "hrt_denoise_device", "hrt_denoise", "hrt_denoise_resolve_u8"]
 HOST_SYMBOLS = ["hrt_host_load_yaml", "hrt_host_free", "hrt_host_flat", "hrt_host_film", "hrt_host_camera", "hrt_host_bvh_depth",
                 "hrt_default_params", "hrt_asset_write_teapot_obj", "hrt_asset_write_bust_obj", "hrt_asset_write_hall_hdr",
                 "hrt_host_write_image", "hrt_host_read_hdr", "hrt_host_read_png", "hrt_host_read_jpeg", "hrt_host_write_hdr", "hrt_host_write_pfm", "hrt_host_read_pfm", "hrt_host_last_error", "hrt_host_set_bvh_builder"]
@@ -201,6 +208,13 @@ _hip.hrt_multi_set_roulette.argtypes = [_vp, C.c_int32, C.c_float]
 _hip.hrt_render_aov_tile.argtypes = [_vp, C.POINTER(Camera), C.POINTER(Params), Rect, _fp]
 _hip.hrt_render_aov_stripes_device.argtypes = [_vp, C.POINTER(Camera), C.POINTER(Params), C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32, _vp]
 _hip.hrt_render_aov_stripes.argtypes = [_vp, C.POINTER(Camera), C.POINTER(Params), C.c_int32, C.c_int32, C.c_int32, _fp, C.c_int32, C.c_int32]
+_hip.hrt_denoise_defaults.argtypes = [C.POINTER(DenoiseParams)]
+_hip.hrt_denoise_defaults.restype = None
+_hip.hrt_denoise_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
+_hip.hrt_denoise_workspace_bytes.restype = C.c_uint64
+_hip.hrt_denoise_device.argtypes = [C.c_int, C.c_int32, C.c_int32, C.POINTER(DenoiseParams), _vp, _vp, _vp, _vp, _vp, _vp]
+_hip.hrt_denoise.argtypes = [C.c_int, C.c_int32, C.c_int32, C.POINTER(DenoiseParams), _fp, _fp, _fp, _fp]
+_hip.hrt_denoise_resolve_u8.argtypes = [C.c_int, _fp, C.c_int64, _u8p]
 _hip.hrt_math_probe.argtypes = [C.c_int, C.c_int32, C.c_int64, _fp, _fp, _fp]
 _hip.hrt_sampler_probe.argtypes = [C.c_int, C.c_uint64, C.c_int64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
 _hip.hrt_env_table_build.argtypes = [_fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp]
@@ -477,6 +491,59 @@ def split_aov(buf):
     if buf.shape[-1] != 8:
         raise ValueError("a feature buffer has 8 floats per pixel")
     return {"albedo": buf[..., 0:3], "alpha": buf[..., 3], "normal": buf[..., 4:7], "depth": buf[..., 7]}
+
+
+def denoise_defaults(**params):
+    """hrt_denoise_defaults, then the given fields (iterations, normal_squarings, sigma_l, sigma_z, albedo_floor) -> DenoiseParams."""
+    p = DenoiseParams()
+    _hip.hrt_denoise_defaults(C.byref(p))
+    names = [n for n, _ in DenoiseParams._fields_]
+    for k, v in params.items():
+        if k not in names:
+            raise TypeError(f"hrt_denoise_params has no field {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def denoise_workspace_bytes(width, height):
+    return int(_hip.hrt_denoise_workspace_bytes(width, height))
+
+
+def denoise(rgb, aov, variance=None, device=0, **params):
+    """The guided denoiser (hrt_denoise, include/hrt.h) on `device`: the linear film rgb [H, W, 3], the raw feature
+    buffer aov [H, W, 8] of render_aov_* (the dict of split_aov is accepted too) and, optionally, the variance of every pixel's mean
+    luminance [H, W] -> the filtered film [H, W, 3].  **params: fields of DenoiseParams that differ from the defaults."""
+    if isinstance(aov, dict):
+        aov = np.concatenate([aov["albedo"], aov["alpha"][..., None], aov["normal"], aov["depth"][..., None]], axis=-1)
+    rgb, aov = _f32(rgb), _f32(aov)
+    if rgb.ndim != 3 or rgb.shape[2] != 3 or aov.shape != rgb.shape[:2] + (8,):
+        raise ValueError("denoise takes rgb [H, W, 3] and aov [H, W, 8]")
+    H, W = rgb.shape[:2]
+    var = None
+    if variance is not None:
+        var = _f32(variance)
+        if var.shape != (H, W):
+            raise ValueError("variance must be [H, W]")
+    p = denoise_defaults(**params)
+    out = np.empty_like(rgb)
+    _check(_hip.hrt_denoise(device, W, H, C.byref(p), _ptr(rgb), _ptr(aov), _ptr(var) if var is not None else None, _ptr(out)))
+    return out
+
+
+def denoise_device(width, height, d_rgb_ptr, d_aov_ptr, d_out_ptr, d_workspace_ptr, d_var_ptr=None, device=0, stream=0, params=None):
+    """Asynchronous (hrt_denoise_device): raw device pointers (e.g. torch tensors' .data_ptr()) to rgb [H, W, 3], aov [H, W, 8], out
+    [H, W, 3] (may be rgb itself), a workspace of denoise_workspace_bytes(width, height) and, optionally, the variance [H, W]."""
+    p = params if params is not None else denoise_defaults()
+    _check(_hip.hrt_denoise_device(device, width, height, C.byref(p), _vp(d_rgb_ptr), _vp(d_aov_ptr), _vp(d_var_ptr) if d_var_ptr else None,
+                                   _vp(d_out_ptr), _vp(d_workspace_ptr), _vp(stream)))
+
+
+def denoise_resolve_u8(rgb_linear, device=0):
+    """hrt_denoise_resolve_u8: DeviceScene.resolve_u8 without a scene -> uint8 array of the same shape."""
+    a = _f32(rgb_linear)
+    out = np.empty(a.shape, dtype=np.uint8)
+    _check(_hip.hrt_denoise_resolve_u8(device, _ptr(a), a.size // 3, _ptr(out, _u8p)))
+    return out
 
 
 class DeviceScene:

@@ -33,7 +33,12 @@
 //     --aov PREFIX (feature buffers, DESIGN.md 4.11: PREFIX.albedo.pfm, PREFIX.normal.pfm, PREFIX.depth.pfm and PREFIX.alpha.pfm, the
 //         first-hit albedo, normal, depth and coverage of the film's camera rays, for a denoiser or a compositor; depth and alpha in all
 //         three channels.  First device only; depends on --lens, --stratified, --quirks, --seed and --size, on nothing else)
-//     --aov-spp N (the samples per pixel of that pass, samples 0 .. N - 1; min(spp, 16) by default; 1 <= N <= spp; needs --aov)
+//     --aov-spp N (the samples per pixel of that pass, samples 0 .. N - 1; min(spp, 16) by default; 1 <= N <= spp; needs --aov or --denoise)
+//     --denoise (the guided denoiser, DESIGN.md 4.12: runs the feature-buffer pass as --aov would -- its files only with --aov PREFIX --
+//         and filters the finished film on the first device with hrt_denoise, spatial variance estimate; the image file and
+//         --dump-linear then hold the filtered film.  Previews and checkpoints stay unfiltered)
+//     --denoise-iterations N (1 .. 8)   --denoise-sigma-l X   --denoise-sigma-z X (finite, > 0; each implies --denoise)
+//     --dump-noisy FILE.pfm (with --denoise: the unfiltered linear film)
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -66,7 +71,10 @@ static void printElapsed(const char* what, std::chrono::high_resolution_clock::t
 int main(int argc, char** argv) {
     auto start = std::chrono::high_resolution_clock::now();
     std::string file = "teapot_scene.yaml";  // main.cpp:146
-    std::string assets, out, makeAssets, dumpLinear, sampleMap, aovPrefix;
+    std::string assets, out, makeAssets, dumpLinear, dumpNoisy, sampleMap, aovPrefix;
+    bool denoise = false;
+    hrt_denoise_params dnp;
+    hrt_denoise_defaults(&dnp);
     long aovSpp = -1;
     bool haveAovSpp = false;
     RenderOptions opt;
@@ -140,6 +148,20 @@ int main(int argc, char** argv) {
             if (end == v || *end != '\0' || aovSpp < 1 || aovSpp > 0x7fffffffl) { std::cerr << "--aov-spp takes an integer >= 1" << std::endl; return 2; }
             haveAovSpp = true;
         }
+        else if (a == "--denoise") denoise = true;
+        else if (a == "--denoise-iterations") {
+            const char* v = next("--denoise-iterations");
+            char* end = nullptr;
+            const long n = std::strtol(v, &end, 10);
+            if (end == v || *end != '\0' || n < 1 || n > 8) { std::cerr << "--denoise-iterations takes an integer from 1 to 8" << std::endl; return 2; }
+            denoise = true; dnp.iterations = (int32_t)n;
+        }
+        else if (a == "--denoise-sigma-l" || a == "--denoise-sigma-z") {
+            const float x = number(a.c_str(), next(a.c_str()));
+            if (!(x > 0.0f) || !std::isfinite(x)) { std::cerr << a << " takes a finite number > 0" << std::endl; return 2; }
+            denoise = true; (a == "--denoise-sigma-l" ? dnp.sigma_l : dnp.sigma_z) = x;
+        }
+        else if (a == "--dump-noisy") dumpNoisy = next("--dump-noisy");
         else if (!haveFile) { file = a; haveFile = true; }
     }
     if (opt.adaptive >= 0.0f) {
@@ -148,7 +170,8 @@ int main(int argc, char** argv) {
         if (opt.min_samples < 2) { std::cerr << "--min-samples must be >= 2" << std::endl; return 2; }
         if (opt.pass_samples <= 0) opt.pass_samples = 16;
     } else if (!sampleMap.empty()) { std::cerr << "--sample-map needs --adaptive" << std::endl; return 2; }
-    if (haveAovSpp && aovPrefix.empty()) { std::cerr << "--aov-spp needs --aov PREFIX" << std::endl; return 2; }
+    if (haveAovSpp && aovPrefix.empty() && !denoise) { std::cerr << "--aov-spp needs --aov PREFIX" << std::endl; return 2; }
+    if (!dumpNoisy.empty() && !denoise) { std::cerr << "--dump-noisy needs --denoise" << std::endl; return 2; }
     if (!makeAssets.empty()) {
         long t = writeTeapotObj(makeAssets + "/teapot.obj", 1.0);
         long b = writeBustObj(makeAssets + "/marble_bust_01.obj", 1.0);
@@ -178,8 +201,8 @@ int main(int argc, char** argv) {
     if (opt.adaptive >= 0.0f && film->getFilm().samples < 2) { std::cerr << "--adaptive needs at least 2 samples per pixel" << std::endl; return 2; }
     if (haveAovSpp && aovSpp > film->getFilm().samples) { std::cerr << "--aov-spp must not exceed the samples per pixel (" << film->getFilm().samples << ")" << std::endl; return 2; }
     std::vector<float> aov;
-    double aov_s = 0.0;
-    if (!aovPrefix.empty()) {
+    double aov_s = 0.0, denoise_s = 0.0;
+    if (!aovPrefix.empty() || denoise) {
         opt.aov_samples = haveAovSpp ? (int)aovSpp : std::min(film->getFilm().samples, 16);
         opt.aov_out = &aov;
         opt.aov_seconds = &aov_s;
@@ -192,6 +215,16 @@ int main(int argc, char** argv) {
     hrt_status st = render(NUM_THREADS, background, world, camera, film, opt, &stats, &seconds);
     if (st != HRT_OK) return -1;
 
+    if (denoise) {   // the finished film, filtered on the first device and resolved as the film resolves itself; the noisy one is kept for --dump-noisy
+        const int w = film->getFilm().width, h = film->getFilm().height;
+        const auto t0 = std::chrono::high_resolution_clock::now();
+        std::vector<float> noisy = film->linear();
+        st = hrt_denoise(0, w, h, &dnp, noisy.data(), aov.data(), nullptr, film->linear().data());
+        if (st == HRT_OK) st = hrt_denoise_resolve_u8(0, film->linear().data(), (int64_t)w * h, film->getPixels());
+        if (st != HRT_OK) { std::cerr << "denoise: " << hrt_status_str(st) << ": " << hrt_last_error() << std::endl; return -1; }
+        denoise_s = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
+        if (!dumpNoisy.empty() && !writePFM(dumpNoisy, noisy.data(), w, h)) { std::cerr << "cannot write " << dumpNoisy << std::endl; return -1; }
+    }
     int r = film->outputFilm();
     if (!dumpLinear.empty() && !writePFM(dumpLinear, film->linear().data(), film->getFilm().width, film->getFilm().height)) {
         std::cerr << "cannot write " << dumpLinear << std::endl;
@@ -223,7 +256,7 @@ int main(int argc, char** argv) {
                              12.0 * film->getFilm().width * film->getFilm().height;
         // wall_s: the reference's own stopwatch (main.cpp:144,184): process start to after the image file is written
         const double wall_s = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - start).count();
-        char extra[224] = "";
+        char extra[320] = "";
         if (opt.adaptive >= 0.0f) {   // the samples adaptive sampling took, and their share of the uniform render's
             const double uniform = (double)film->getFilm().width * film->getFilm().height * film->getFilm().samples;
             std::snprintf(extra, sizeof(extra), ", \"adaptive_threshold\": %g, \"samples_taken\": %llu, \"sample_fraction\": %.6f",
@@ -233,9 +266,13 @@ int main(int argc, char** argv) {
             const size_t k = std::strlen(extra);
             std::snprintf(extra + k, sizeof(extra) - k, ", \"shadow_rays\": %llu", (unsigned long long)stats.shadow_rays);
         }
-        if (!aovPrefix.empty()) {     // the feature-buffer pass: its samples per pixel and the wall time of the call
+        if (opt.aov_samples > 0) {    // the feature-buffer pass: its samples per pixel and the wall time of the call
             const size_t k = std::strlen(extra);
             std::snprintf(extra + k, sizeof(extra) - k, ", \"aov_spp\": %d, \"aov_s\": %.6f", opt.aov_samples, aov_s);
+        }
+        if (denoise) {                // the filter and the resolve of the filtered film: the wall time of the two calls, copies included
+            const size_t k = std::strlen(extra);
+            std::snprintf(extra + k, sizeof(extra) - k, ", \"denoise_s\": %.6f", denoise_s);
         }
         std::printf("{\"rays\": %llu, \"samples\": %llu, \"box_tests\": %llu, \"tri_tests\": %llu, \"render_s\": %.6f, "
                     "\"kernel_ms\": %.3f, \"mrays_per_s\": %.3f, \"msamples_per_s\": %.3f, \"algorithmic_gb_per_s\": %.3f, "

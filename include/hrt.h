@@ -455,6 +455,70 @@ hrt_status hrt_render_aov_stripes_device(hrt_scene* scene, const hrt_camera* cam
 hrt_status hrt_render_aov_stripes(hrt_scene* scene, const hrt_camera* cam, const hrt_params* params, int32_t rows_per_block, int32_t rank,
                                   int32_t n_ranks, float* out, int32_t sample_first, int32_t sample_count);
 
+/* ---- guided denoiser --------------------------------------
+ * An edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) with a variance-guided luminance weight (the spatial part of SVGF,
+ * Schied et al. 2017) over albedo-demodulated radiance, guided by the feature buffers above.  It needs no scene.  Everything is fp32 and
+ * uses only + - * /, sqrtf, fabsf and comparisons, evaluated left to right in the order written here without fused multiply-adds, so
+ * that a restatement of these words with IEEE fp32 operations gives the same bits (tests/denoise_np.py).  In this text max(a, b) means
+ * (a > b ? a : b) and max(0, x) means (x > 0 ? x : 0): a NaN gives the second operand.
+ *
+ * Inputs, whole-film images in film order (row 0 = top), W x H pixels:
+ *   rgb   3 floats per pixel: the film's linear means c
+ *   aov   8 floats per pixel: the buffer of hrt_render_aov_*, A = albedo r, g, b, alpha and B = normal x, y, z, depth
+ *   var   optional (NULL: estimated, see below), 1 float per pixel: the variance of the pixel's mean luminance; from the buffers of
+ *         hrt_render_stripes_adaptive that is max(0, (sq - n m m) / (n - 1)) / n with m = Y(sums) / n
+ * Y(r, g, b) = 0.2126f * r + 0.7152f * g + 0.0722f * b.
+ *
+ * Prepare, per pixel p:
+ *   af_k = a_k > albedo_floor ? a_k : albedo_floor  (a NaN albedo becomes the floor)     valid = all three c_k are finite
+ *   e_k = c_k / af_k                 l = Y(e)
+ *   d = n.x * n.x + n.y * n.y + n.z * n.z        nh = d > 0 ? n * (1.0f / sqrtf(d)) : (0, 0, 0)
+ *   z = alpha > 0 ? depth / alpha : 0
+ *   var given:   v = (var > 0 ? var : 0) / (Y(af) * Y(af))
+ *   var absent:  over the 7 x 7 window at spacing 1 around p, its in-film valid pixels q in row-major order (p among them):
+ *                s1 += l_q, s2 += l_q * l_q, n += 1;  then m = s1 / n and v = max(0, s2 / n - m * m)
+ *
+ * Iteration j = 0 .. iterations - 1, with s = 1 << j, from the image (e, v) to a second one (ping-pong):
+ *   an invalid centre is copied through unchanged.  Otherwise
+ *   vbar = (sum of g * v_q) / (sum of g) over the in-film valid q = p + (dx, dy), dy outer and dx inner over -1 .. 1,
+ *          g = b[|dx|] * b[|dy|], b = (0.5, 0.25);   sd = sqrtf(vbar)
+ *   taps q = p + s * (dx, dy), dy outer and dx inner over -2 .. 2; taps outside the film and invalid taps are skipped:
+ *     h = k[|dx|] * k[|dy|], k = (0.375, 0.25, 0.0625)
+ *     the centre tap: w = h.   Every other tap: w = h * wn * wz * wl with
+ *     wn = 1 when nh_p and nh_q are both zero (all three components == 0), 0 when exactly one is, otherwise
+ *          t = max(0, nh_p.x * nh_q.x + nh_p.y * nh_q.y + nh_p.z * nh_q.z), then t = t * t done normal_squarings times
+ *     wz = r(fabsf(z_p - z_q) / (sigma_z * max(z_p, z_q) + 1e-6f))
+ *     wl = r(fabsf(l_p - l_q) / (sigma_l * sd + 1e-6f)), l = Y(e) of the iteration's input image
+ *     r(x) = u * u with u = max(0, 1.0f - x)
+ *     sum_k += w * e_q,k     sw += w     sv += (w * w) * v_q
+ *   e'_k = sum_k / sw and v' = sv / (sw * sw); sw >= 0.140625 (the centre tap) always.
+ *
+ * Finish: out_k = valid ? e_k * af_k : c_k.  An invalid pixel keeps its bits and never contributes to another pixel.
+ *
+ * Temporal accumulation, specular follow-through and an exp-shaped falloff are not part of it. */
+typedef struct hrt_denoise_params {
+    int32_t iterations;       /* 1 .. 8; default 5: the last iteration's taps reach 2 << (iterations - 1) pixels */
+    int32_t normal_squarings; /* 0 .. 10; default 7: the normal weight is the clamped cosine to the power 1 << normal_squarings */
+    float sigma_l;            /* finite, > 0; default 2.5: luminance differences up to sigma_l standard deviations get a weight */
+    float sigma_z;            /* finite, > 0; default 0.5: relative depth differences up to sigma_z get a weight */
+    float albedo_floor;       /* finite, > 0; default 0.01: the smallest albedo the radiance is divided by */
+} hrt_denoise_params;
+/* Fills in the defaults. */
+void hrt_denoise_defaults(hrt_denoise_params* params);
+/* The bytes hrt_denoise_device needs as workspace for a W x H film (48 per pixel); 0 when W or H is below 1 or W x H above 2^30. */
+uint64_t hrt_denoise_workspace_bytes(int32_t W, int32_t H);
+/* Asynchronous, on HIP stream `stream` of `device`: filters the DEVICE image d_rgb into d_out (d_out == d_rgb is allowed; no other
+ * overlap is).  d_var may be NULL.  d_aov and d_workspace must be 16-byte aligned.  HRT_ERR_INVALID, with a message, for a NULL
+ * argument, W or H below 1, more than 2^30 pixels, a parameter outside its range or NaN, or a misaligned pointer -- decided before any
+ * device is touched, and the output is left untouched. */
+hrt_status hrt_denoise_device(int device, int32_t W, int32_t H, const hrt_denoise_params* params, const float* d_rgb, const float* d_aov,
+                              const float* d_var, float* d_out, void* d_workspace, void* stream);
+/* Blocking, HOST buffers (out == rgb is allowed); allocates its own workspace on `device`.  The same refusals. */
+hrt_status hrt_denoise(int device, int32_t W, int32_t H, const hrt_denoise_params* params, const float* rgb, const float* aov,
+                       const float* var, float* out);
+/* hrt_resolve_u8 for a caller that holds no hrt_scene (a filtered film after its scene is gone): the same bytes.  Blocking, host buffers. */
+hrt_status hrt_denoise_resolve_u8(int device, const float* rgb_linear, int64_t n_pixels, uint8_t* out_rgb8);
+
 /* ---- multi-GPU session -----------------------------------
  * The reference's render() (main.cpp:81-140) has one parallel loop over all pixels of the film (main.cpp:111-135, no state
  * shared between pixels).  Here the flattened scene is replicated on `n_devices` GPUs of THIS process (`devices` = their
