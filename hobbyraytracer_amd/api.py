@@ -147,7 +147,9 @@ HIP_SYMBOLS = ["hrt_device_count", "hrt_scene_create", "hrt_scene_destroy", "hrt
                "hrt_render_stripes_adaptive_device", "hrt_render_stripes_adaptive", "hrt_adaptive_mean_device", "hrt_env_table_build",
                "hrt_emitter_table_build", "hrt_scene_set_roulette", "hrt_multi_set_roulette",
                "hrt_render_aov_tile", "hrt_render_aov_stripes_device", "hrt_render_aov_stripes",
-               "hrt_denoise_defaults", "hrt_denoise_workspace_bytes", "hrt_denoise_device", "hrt_denoise", "hrt_denoise_resolve_u8"]
+               "hrt_denoise_defaults", "hrt_denoise_workspace_bytes", "hrt_denoise_device", "hrt_denoise", "hrt_denoise_resolve_u8",
+               "hrt_variance_state_bytes", "hrt_variance_fold_device", "hrt_variance_finish_device", "hrt_adaptive_variance_device",
+               "hrt_variance_fold", "hrt_variance_finish", "hrt_adaptive_variance"]
 HOST_SYMBOLS = ["hrt_host_load_yaml", "hrt_host_free", "hrt_host_flat", "hrt_host_film", "hrt_host_camera", "hrt_host_bvh_depth",
                 "hrt_default_params", "hrt_asset_write_teapot_obj", "hrt_asset_write_bust_obj", "hrt_asset_write_hall_hdr",
                 "hrt_host_write_image", "hrt_host_read_hdr", "hrt_host_read_png", "hrt_host_read_jpeg", "hrt_host_write_hdr", "hrt_host_write_pfm", "hrt_host_read_pfm", "hrt_host_last_error", "hrt_host_set_bvh_builder"]
@@ -215,6 +217,14 @@ _hip.hrt_denoise_workspace_bytes.restype = C.c_uint64
 _hip.hrt_denoise_device.argtypes = [C.c_int, C.c_int32, C.c_int32, C.POINTER(DenoiseParams), _vp, _vp, _vp, _vp, _vp, _vp]
 _hip.hrt_denoise.argtypes = [C.c_int, C.c_int32, C.c_int32, C.POINTER(DenoiseParams), _fp, _fp, _fp, _fp]
 _hip.hrt_denoise_resolve_u8.argtypes = [C.c_int, _fp, C.c_int64, _u8p]
+_hip.hrt_variance_state_bytes.argtypes = [C.c_int64]
+_hip.hrt_variance_state_bytes.restype = C.c_uint64
+_hip.hrt_variance_fold_device.argtypes = [C.c_int, C.c_int64, _vp, C.c_float, C.c_int32, C.c_int32, _vp, _vp]
+_hip.hrt_variance_finish_device.argtypes = [C.c_int, C.c_int64, _vp, C.c_int32, C.c_int32, _vp, _vp]
+_hip.hrt_adaptive_variance_device.argtypes = [C.c_int, C.c_int64, _vp, _vp, _vp, _vp, _vp]
+_hip.hrt_variance_fold.argtypes = [C.c_int, C.c_int64, _fp, C.c_float, C.c_int32, C.c_int32, _fp]
+_hip.hrt_variance_finish.argtypes = [C.c_int, C.c_int64, _fp, C.c_int32, C.c_int32, _fp]
+_hip.hrt_adaptive_variance.argtypes = [C.c_int, C.c_int64, _fp, _fp, C.POINTER(C.c_int32), _fp]
 _hip.hrt_math_probe.argtypes = [C.c_int, C.c_int32, C.c_int64, _fp, _fp, _fp]
 _hip.hrt_sampler_probe.argtypes = [C.c_int, C.c_uint64, C.c_int64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
 _hip.hrt_env_table_build.argtypes = [_fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp]
@@ -546,6 +556,80 @@ def denoise_resolve_u8(rgb_linear, device=0):
     return out
 
 
+def variance_state_bytes(n_pixels):
+    """hrt_variance_state_bytes: the bytes of the batch-means state of n_pixels pixels (8 each)."""
+    return int(_hip.hrt_variance_state_bytes(n_pixels))
+
+
+def variance_batches(samples, batches):
+    """The sample ranges [(first, count), ...] of a render split into `batches` passes for the measured variance: range j starts at
+    j * ceil(samples / batches) and the last one takes what is left (fewer than `batches` ranges when they run out first)."""
+    if samples < 1 or batches < 1:
+        raise ValueError("samples and batches must be >= 1")
+    step = -(-samples // batches)
+    return [(s, min(step, samples - s)) for s in range(0, samples, step)]
+
+
+def variance_fold(rgb, samples_before, samples_batch, state=None, scale=1.0, device=0):
+    """One fold of the measured variance (hrt_variance_fold, include/hrt.h) on `device`: rgb [..., 3] is the accumulation
+    buffer after a batch of samples_batch samples that follows samples_before earlier ones; scale is 1 while it holds undivided sums and
+    the sample count for the buffer whose last pass has divided.  state [..., 2] = (yprev, M2) is the array the fold before returned
+    (not read, and allocated when None, for samples_before == 0).  Returns the new state, a new array."""
+    rgb = _f32(rgb)
+    if rgb.ndim < 1 or rgb.shape[-1] != 3:
+        raise ValueError("variance_fold takes rgb [..., 3]")
+    shape = rgb.shape[:-1] + (2,)
+    if state is None:
+        if samples_before > 0:
+            raise ValueError("samples_before > 0 continues a measurement: pass the state of the folds before")
+        out = np.zeros(shape, np.float32)
+    else:
+        out = np.array(state, dtype=np.float32, order="C")
+        if out.shape != shape:
+            raise ValueError("state must be [..., 2] over the pixels of rgb")
+    _check(_hip.hrt_variance_fold(device, rgb.size // 3, _ptr(rgb), scale, samples_before, samples_batch, _ptr(out)))
+    return out
+
+
+def variance_finish(state, samples, batches, device=0):
+    """hrt_variance_finish: the state [..., 2] after `batches` folds over `samples` samples -> the variance of every pixel's mean
+    luminance [...], what denoise() takes as `variance`."""
+    state = _f32(state)
+    if state.ndim < 1 or state.shape[-1] != 2:
+        raise ValueError("variance_finish takes state [..., 2]")
+    var = np.empty(state.shape[:-1], np.float32)
+    _check(_hip.hrt_variance_finish(device, state.size // 2, _ptr(state), samples, batches, _ptr(var)))
+    return var
+
+
+def adaptive_variance(sums, sq, count, device=0):
+    """hrt_adaptive_variance: the variance of every pixel's mean luminance [...] from the buffers of an adaptive render, sums [..., 3],
+    sq [...] and count [...] (int32); 0 where a pixel has fewer than 2 samples."""
+    sums, sq = _f32(sums), _f32(sq)
+    count = np.ascontiguousarray(count, dtype=np.int32)
+    if sums.shape != sq.shape + (3,) or count.shape != sq.shape:
+        raise ValueError("adaptive_variance takes sums [..., 3], sq [...] and count [...]")
+    var = np.empty(sq.shape, np.float32)
+    _check(_hip.hrt_adaptive_variance(device, sq.size, _ptr(sums), _ptr(sq), _ptr(count, C.POINTER(C.c_int32)), _ptr(var)))
+    return var
+
+
+def variance_fold_device(n_pixels, d_rgb_ptr, samples_before, samples_batch, d_state_ptr, scale=1.0, device=0, stream=0):
+    """Asynchronous (hrt_variance_fold_device): raw device pointers (e.g. torch tensors' .data_ptr()) to rgb [n_pixels, 3] and the state
+    [n_pixels, 2] (variance_state_bytes(n_pixels) bytes, 8-byte aligned)."""
+    _check(_hip.hrt_variance_fold_device(device, n_pixels, _vp(d_rgb_ptr), scale, samples_before, samples_batch, _vp(d_state_ptr), _vp(stream)))
+
+
+def variance_finish_device(n_pixels, d_state_ptr, samples, batches, d_var_ptr, device=0, stream=0):
+    """Asynchronous (hrt_variance_finish_device): the state [n_pixels, 2] -> the variance [n_pixels]."""
+    _check(_hip.hrt_variance_finish_device(device, n_pixels, _vp(d_state_ptr), samples, batches, _vp(d_var_ptr), _vp(stream)))
+
+
+def adaptive_variance_device(n_pixels, d_sums_ptr, d_sq_ptr, d_count_ptr, d_var_ptr, device=0, stream=0):
+    """Asynchronous (hrt_adaptive_variance_device): the adaptive render's device buffers -> the variance [n_pixels]."""
+    _check(_hip.hrt_adaptive_variance_device(device, n_pixels, _vp(d_sums_ptr), _vp(d_sq_ptr), _vp(d_count_ptr), _vp(d_var_ptr), _vp(stream)))
+
+
 class DeviceScene:
     """hrt_scene: the flat scene resident on one GPU."""
 
@@ -617,6 +701,36 @@ class DeviceScene:
     def render_stripes_accumulate_device(self, cam, params, rows_per_block, rank, n_ranks, d_accum_ptr, sample_first, sample_count, stream=0):
         _check(_hip.hrt_render_stripes_accumulate_device(self._h, C.byref(cam), C.byref(params), rows_per_block, rank, n_ranks,
                                                          _vp(d_accum_ptr), sample_first, sample_count, _vp(stream)))
+
+    def render_stripes_with_variance(self, cam, params, batches=4, rows_per_block=8, rank=0, n_ranks=1):
+        """The film stripes of render_stripes and the measured variance of every pixel's mean luminance, device
+        resident: hrt_render_stripes_accumulate_device over the sample ranges of variance_batches(params.samples, batches) with an
+        hrt_variance_fold_device after each and an hrt_variance_finish_device at the end, all on one stream of a torch device buffer
+        with no host round trip in between.  -> (film [rows, W, 3], var [rows, W]) fp32; the film is render_stripes' bits.
+        ValueError when fewer than two batches exist (params.samples < 2 or batches < 2)."""
+        import torch
+        ranges = variance_batches(params.samples, batches)
+        if len(ranges) < 2:
+            raise ValueError("the measured variance needs at least two batches: samples >= 2 and batches >= 2")
+        rows = stripe_rows(params.height, rows_per_block, rank, n_ranks)
+        n = rows * params.width
+        dev = torch.device("cuda", self.device)
+        accum = torch.empty((rows, params.width, 3), dtype=torch.float32, device=dev)
+        state = torch.empty((rows, params.width, 2), dtype=torch.float32, device=dev)
+        var = torch.empty((rows, params.width), dtype=torch.float32, device=dev)
+        if n == 0:
+            return accum.cpu().numpy(), var.cpu().numpy()
+        stream = torch.cuda.Stream(device=dev)
+        with torch.cuda.stream(stream):
+            s = stream.cuda_stream
+            for first, count in ranges:
+                self.render_stripes_accumulate_device(cam, params, rows_per_block, rank, n_ranks, accum.data_ptr(), first, count, stream=s)
+                last = first + count == params.samples
+                variance_fold_device(n, accum.data_ptr(), first, count, state.data_ptr(), scale=float(params.samples) if last else 1.0,
+                                     device=self.device, stream=s)
+            variance_finish_device(n, state.data_ptr(), params.samples, len(ranges), var.data_ptr(), device=self.device, stream=s)
+        stream.synchronize()
+        return accum.cpu().numpy(), var.cpu().numpy()
 
     def render_stripes_adaptive(self, cam, params, rows_per_block, rank, n_ranks, adaptive, pass_index, sums=None, sq=None, count=None):
         """One adaptive pass (hrt_render_stripes_adaptive) -> (sums, sq, count, active, Stats).  Pass 0 allocates the buffers when

@@ -39,6 +39,15 @@
 //         --dump-linear then hold the filtered film.  Previews and checkpoints stay unfiltered)
 //     --denoise-iterations N (1 .. 8)   --denoise-sigma-l X   --denoise-sigma-z X (finite, > 0; each implies --denoise)
 //     --dump-noisy FILE.pfm (with --denoise: the unfiltered linear film)
+//     --denoise-variance spatial|measured (implies --denoise; DESIGN.md 4.13.  spatial, the default: the filter estimates the variance
+//         from a 7 x 7 window.  measured: it is given the variance of every pixel's mean luminance -- with --adaptive from the adaptive
+//         render's buffers, otherwise from the batch means of the render's passes: the passes of --progressive N or, without it,
+//         --denoise-batches K passes (--max-passes counts them).  The film is the same bits however it is batched.  After --resume the
+//         resumed sums are the first batch; with fewer than two batches (--spp 1, nothing left to render) the filter falls back to the
+//         spatial estimate and says so.  Without --denoise-sigma-l the filter then takes sigma_l = 6 instead of 2.5.  With --stratified
+//         the batches are not independent and the measured variance is too large: the filter smooths more)
+//     --denoise-batches K (2 .. 64, default 4, reduced to the samples per pixel; implies --denoise-variance measured)
+//     --dump-variance FILE.pfm (with --denoise-variance measured: the variance in all three channels)
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -58,6 +67,10 @@
 
 using namespace hrthost;
 
+// sigma_l under --denoise-variance measured when --denoise-sigma-l is not given: the lowest worse-of-two error ratio of the sweep of
+// DESIGN.md 4.13 at K = 4 (hrt_denoise_defaults keeps 2.5, the best value for the spatial estimate)
+constexpr float kMeasuredSigmaL = 6.0f;
+
 constexpr int NUM_THREADS = 12;  // main.cpp:34 (unused by render, as in the reference)
 
 static void printElapsed(const char* what, std::chrono::high_resolution_clock::time_point start) {
@@ -71,8 +84,9 @@ static void printElapsed(const char* what, std::chrono::high_resolution_clock::t
 int main(int argc, char** argv) {
     auto start = std::chrono::high_resolution_clock::now();
     std::string file = "teapot_scene.yaml";  // main.cpp:146
-    std::string assets, out, makeAssets, dumpLinear, dumpNoisy, sampleMap, aovPrefix;
-    bool denoise = false;
+    std::string assets, out, makeAssets, dumpLinear, dumpNoisy, sampleMap, aovPrefix, dumpVariance;
+    bool denoise = false, measured = false, haveVarianceMode = false, haveSigmaL = false;
+    long denoiseBatches = 4;
     hrt_denoise_params dnp;
     hrt_denoise_defaults(&dnp);
     long aovSpp = -1;
@@ -160,7 +174,22 @@ int main(int argc, char** argv) {
             const float x = number(a.c_str(), next(a.c_str()));
             if (!(x > 0.0f) || !std::isfinite(x)) { std::cerr << a << " takes a finite number > 0" << std::endl; return 2; }
             denoise = true; (a == "--denoise-sigma-l" ? dnp.sigma_l : dnp.sigma_z) = x;
+            if (a == "--denoise-sigma-l") haveSigmaL = true;
         }
+        else if (a == "--denoise-variance") {
+            const std::string v = next("--denoise-variance");
+            if (v != "spatial" && v != "measured") { std::cerr << "--denoise-variance takes spatial or measured" << std::endl; return 2; }
+            denoise = true; measured = v == "measured"; haveVarianceMode = true;
+        }
+        else if (a == "--denoise-batches") {
+            const char* v = next("--denoise-batches");
+            char* end = nullptr;
+            denoiseBatches = std::strtol(v, &end, 10);
+            if (end == v || *end != '\0' || denoiseBatches < 2 || denoiseBatches > 64) { std::cerr << "--denoise-batches takes an integer from 2 to 64" << std::endl; return 2; }
+            denoise = true;
+            if (!haveVarianceMode) measured = true;
+        }
+        else if (a == "--dump-variance") dumpVariance = next("--dump-variance");
         else if (a == "--dump-noisy") dumpNoisy = next("--dump-noisy");
         else if (!haveFile) { file = a; haveFile = true; }
     }
@@ -172,6 +201,7 @@ int main(int argc, char** argv) {
     } else if (!sampleMap.empty()) { std::cerr << "--sample-map needs --adaptive" << std::endl; return 2; }
     if (haveAovSpp && aovPrefix.empty() && !denoise) { std::cerr << "--aov-spp needs --aov PREFIX" << std::endl; return 2; }
     if (!dumpNoisy.empty() && !denoise) { std::cerr << "--dump-noisy needs --denoise" << std::endl; return 2; }
+    if (!dumpVariance.empty() && !measured) { std::cerr << "--dump-variance needs --denoise-variance measured" << std::endl; return 2; }
     if (!makeAssets.empty()) {
         long t = writeTeapotObj(makeAssets + "/teapot.obj", 1.0);
         long b = writeBustObj(makeAssets + "/marble_bust_01.obj", 1.0);
@@ -201,7 +231,13 @@ int main(int argc, char** argv) {
     if (opt.adaptive >= 0.0f && film->getFilm().samples < 2) { std::cerr << "--adaptive needs at least 2 samples per pixel" << std::endl; return 2; }
     if (haveAovSpp && aovSpp > film->getFilm().samples) { std::cerr << "--aov-spp must not exceed the samples per pixel (" << film->getFilm().samples << ")" << std::endl; return 2; }
     std::vector<float> aov;
-    double aov_s = 0.0, denoise_s = 0.0;
+    double aov_s = 0.0, denoise_s = 0.0, variance_s = 0.0;
+    std::vector<float> variance;
+    if (measured) {
+        opt.variance_out = &variance;
+        opt.variance_seconds = &variance_s;
+        opt.variance_batches = (int)denoiseBatches;
+    }
     if (!aovPrefix.empty() || denoise) {
         opt.aov_samples = haveAovSpp ? (int)aovSpp : std::min(film->getFilm().samples, 16);
         opt.aov_out = &aov;
@@ -219,11 +255,20 @@ int main(int argc, char** argv) {
         const int w = film->getFilm().width, h = film->getFilm().height;
         const auto t0 = std::chrono::high_resolution_clock::now();
         std::vector<float> noisy = film->linear();
-        st = hrt_denoise(0, w, h, &dnp, noisy.data(), aov.data(), nullptr, film->linear().data());
+        const bool haveVariance = measured && variance.size() == (size_t)w * h;
+        if (measured && !haveVariance) std::cerr << "denoise: fewer than two batches of samples to measure the variance from: using the spatial estimate" << std::endl;
+        if (haveVariance && !haveSigmaL) dnp.sigma_l = kMeasuredSigmaL;
+        st = hrt_denoise(0, w, h, &dnp, noisy.data(), aov.data(), haveVariance ? variance.data() : nullptr, film->linear().data());
         if (st == HRT_OK) st = hrt_denoise_resolve_u8(0, film->linear().data(), (int64_t)w * h, film->getPixels());
         if (st != HRT_OK) { std::cerr << "denoise: " << hrt_status_str(st) << ": " << hrt_last_error() << std::endl; return -1; }
         denoise_s = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
         if (!dumpNoisy.empty() && !writePFM(dumpNoisy, noisy.data(), w, h)) { std::cerr << "cannot write " << dumpNoisy << std::endl; return -1; }
+        if (!dumpVariance.empty() && !haveVariance) std::cerr << "--dump-variance: no variance was measured, " << dumpVariance << " is not written" << std::endl;
+        if (!dumpVariance.empty() && haveVariance) {
+            std::vector<float> img((size_t)w * h * 3);
+            for (size_t i = 0; i < (size_t)w * h; ++i) img[3 * i] = img[3 * i + 1] = img[3 * i + 2] = variance[i];
+            if (!writePFM(dumpVariance, img.data(), w, h)) { std::cerr << "cannot write " << dumpVariance << std::endl; return -1; }
+        }
     }
     int r = film->outputFilm();
     if (!dumpLinear.empty() && !writePFM(dumpLinear, film->linear().data(), film->getFilm().width, film->getFilm().height)) {
@@ -256,7 +301,7 @@ int main(int argc, char** argv) {
                              12.0 * film->getFilm().width * film->getFilm().height;
         // wall_s: the reference's own stopwatch (main.cpp:144,184): process start to after the image file is written
         const double wall_s = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - start).count();
-        char extra[320] = "";
+        char extra[384] = "";
         if (opt.adaptive >= 0.0f) {   // the samples adaptive sampling took, and their share of the uniform render's
             const double uniform = (double)film->getFilm().width * film->getFilm().height * film->getFilm().samples;
             std::snprintf(extra, sizeof(extra), ", \"adaptive_threshold\": %g, \"samples_taken\": %llu, \"sample_fraction\": %.6f",
@@ -273,6 +318,10 @@ int main(int argc, char** argv) {
         if (denoise) {                // the filter and the resolve of the filtered film: the wall time of the two calls, copies included
             const size_t k = std::strlen(extra);
             std::snprintf(extra + k, sizeof(extra) - k, ", \"denoise_s\": %.6f", denoise_s);
+        }
+        if (measured) {               // the measured variance: the wall time of its folds on the first device, copies included
+            const size_t k = std::strlen(extra);
+            std::snprintf(extra + k, sizeof(extra) - k, ", \"variance_s\": %.6f", variance_s);
         }
         std::printf("{\"rays\": %llu, \"samples\": %llu, \"box_tests\": %llu, \"tri_tests\": %llu, \"render_s\": %.6f, "
                     "\"kernel_ms\": %.3f, \"mrays_per_s\": %.3f, \"msamples_per_s\": %.3f, \"algorithmic_gb_per_s\": %.3f, "

@@ -159,6 +159,12 @@ hrt_status renderAdaptive(const hrt_flat_scene& flat, const hrt_camera& cam, hrt
         mean();
         st = hrt_resolve_u8(sc, lin.data(), numPixels, film->getPixels());
     }
+    if (st == HRT_OK && opt.variance_out) {   // the measured variance, from the buffers the stopping rule itself reads
+        const auto v0 = std::chrono::high_resolution_clock::now();
+        opt.variance_out->assign((size_t)numPixels, 0.0f);
+        st = hrt_adaptive_variance(0, numPixels, sums.data(), sq.data(), count.data(), opt.variance_out->data());
+        if (opt.variance_seconds) *opt.variance_seconds = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - v0).count();
+    }
     if (st != HRT_OK) std::cerr << "\nadaptive render failed: " << hrt_status_str(st) << ": " << hrt_last_error() << std::endl;
     const auto t1 = std::chrono::high_resolution_clock::now();
     if (render_seconds) *render_seconds = std::chrono::duration<double>(t1 - t0).count();
@@ -298,7 +304,28 @@ hrt_status render(int /*nThreads*/, const std::shared_ptr<Texture> background, c
         have_resume = true;
         std::cout << "\rResumed at sample " << s_done << "/" << f.samples << std::endl;
     }
-    const int pass = opt.pass_samples > 0 ? opt.pass_samples : f.samples;
+    // The measured variance (hrt.h hrt_variance_*): the gathered sums are folded on the first device after every pass; without
+    // --progressive the render is split into variance_batches passes for it.  Resumed sums are the first batch.
+    const bool measure = opt.variance_out != nullptr;
+    std::vector<float> vstate;
+    int vbatches = 0;
+    double vseconds = 0.0;
+    auto fold = [&](float scale, int before, int count) -> hrt_status {
+        const auto v0 = std::chrono::high_resolution_clock::now();
+        if (vstate.empty()) vstate.assign((size_t)numPixels * 2, 0.0f);
+        const hrt_status fs = hrt_variance_fold(0, numPixels, sums.data(), scale, before, count, vstate.data());
+        vseconds += std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - v0).count();
+        if (fs == HRT_OK) ++vbatches;
+        else std::cerr << "\nvariance: " << hrt_status_str(fs) << ": " << hrt_last_error() << std::endl;
+        return fs;
+    };
+    if (measure) opt.variance_out->clear();
+    if (measure && s_done > 0 && s_done < f.samples && (st = fold(1.0f, 0, s_done)) != HRT_OK) { cleanup(); return st; }
+    int pass = opt.pass_samples > 0 ? opt.pass_samples : f.samples;
+    if (measure && opt.pass_samples <= 0 && opt.variance_batches > 1) {
+        const int K = std::min(opt.variance_batches, f.samples);
+        pass = (f.samples + K - 1) / K;
+    }
     hrt_stats total{};
     int passes = 0;
     bool resolved = false;
@@ -315,6 +342,7 @@ hrt_status render(int /*nThreads*/, const std::shared_ptr<Texture> background, c
         }
         resolved = true;
         addPassStats(total, ps);
+        if (measure && (st = fold(s_done + n == f.samples ? static_cast<float>(f.samples) : 1.0f, s_done, n)) != HRT_OK) { cleanup(); return st; }
         s_done += n;
         pathsBefore.store((long long)numPixels * (long long)s_done);
         if (!opt.checkpoint.empty()) {
@@ -329,7 +357,7 @@ hrt_status render(int /*nThreads*/, const std::shared_ptr<Texture> background, c
         }
     }
     const auto t1 = std::chrono::high_resolution_clock::now();
-    if (render_seconds) *render_seconds = std::chrono::duration<double>(t1 - t0).count();
+    if (render_seconds) *render_seconds = std::chrono::duration<double>(t1 - t0).count() - vseconds;   // (the folds are variance_seconds')
     st = HRT_OK;
     if (s_done >= f.samples && resolved) lin = sums;   // the last pass divided (main.cpp:126): the sums are the means now
     else if (!resolved) {                              // nothing rendered in this call (resume of a stopped render with --max-passes 0 ...)
@@ -339,6 +367,14 @@ hrt_status render(int /*nThreads*/, const std::shared_ptr<Texture> background, c
         const float k = static_cast<float>(s_done > 0 && s_done < f.samples ? s_done : 1);
         for (size_t i = 0; i < lin.size(); ++i) lin[i] = sums[i] / k;
     }
+    if (st == HRT_OK && measure && vbatches >= 2) {   // fewer than two batches: *variance_out stays empty and the caller falls back
+        const auto v0 = std::chrono::high_resolution_clock::now();
+        opt.variance_out->assign((size_t)numPixels, 0.0f);
+        st = hrt_variance_finish(0, numPixels, vstate.data(), s_done, vbatches, opt.variance_out->data());
+        vseconds += std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - v0).count();
+        if (st != HRT_OK) std::cerr << "\nvariance: " << hrt_status_str(st) << ": " << hrt_last_error() << std::endl;
+    }
+    if (opt.variance_seconds) *opt.variance_seconds = vseconds;
     stopReporter();
     std::cout << "\rPixels rendered: " << numPixels << "/" << numPixels << std::flush << "\n";
     hrt_multi_destroy(multi);

@@ -54,6 +54,16 @@ struct RenderOptions {
     int aov_samples = 0;
     std::vector<float>* aov_out = nullptr;
     double* aov_seconds = nullptr;
+    // Measured variance (--denoise-variance measured, hrt.h hrt_variance_*): with variance_out set the render measures
+    // the variance of every pixel's mean luminance -- an adaptive render from its own buffers (hrt_adaptive_variance), any other from
+    // the batch means of its passes: the passes of pass_samples or, without them, variance_batches passes (range j starts at
+    // j * ceil(samples / variance_batches)) taken for this purpose only, without previews; resumed sums count as the first batch.  The
+    // gathered whole-film sums are folded on the first device after every pass, whatever `gpus` is; the film's bits do not depend on
+    // any of it.  *variance_out gets width * height floats in film order, or stays empty when fewer than two batches existed;
+    // *variance_seconds (optional) the wall time of the folds, copies included.  Checkpoints do not hold the state.
+    int variance_batches = 0;
+    std::vector<float>* variance_out = nullptr;
+    double* variance_seconds = nullptr;
 };
 
 // render() of main.cpp:81-140.  nThreads is accepted and unused, exactly as in

@@ -519,6 +519,53 @@ hrt_status hrt_denoise(int device, int32_t W, int32_t H, const hrt_denoise_param
 /* hrt_resolve_u8 for a caller that holds no hrt_scene (a filtered film after its scene is gone): the same bytes.  Blocking, host buffers. */
 hrt_status hrt_denoise_resolve_u8(int device, const float* rgb_linear, int64_t n_pixels, uint8_t* out_rgb8);
 
+/* ---- measured variance ------------------------------------
+ * The `var` input of hrt_denoise, measured instead of guessed: the variance of every pixel's mean luminance, from the batch means of a
+ * render taken in passes (hrt_render_stripes_accumulate*, hrt_multi_render: any batching ends in the one-shot film's bits, so the batches
+ * cost no sample) or from the buffers of an adaptive render.  It needs no scene.  Everything is fp32 and uses only + - * / and
+ * comparisons, evaluated in the order written here without fused multiply-adds, so that a restatement of these words with IEEE fp32
+ * operations gives the same bits (tests/variance_np.py).  Y is the luminance of the denoiser's text above, max(0, x) means
+ * (x > 0 ? x : 0): a NaN gives 0.  Pixels are independent of each other; the buffers may have any layout (film order, stripes).
+ *
+ * Fold, after a batch of c = samples_batch samples that follows done = samples_before earlier ones, per pixel:
+ *   rgb    3 floats: the accumulation buffer after the batch
+ *   scale  1 while the buffer holds undivided sums; (float)samples for the buffer whose last pass has divided by `samples`
+ *   state  2 floats: (yprev, M2), the luminance of the sums before this batch and the running sum of squared deviations
+ *   y = Y(rgb) * scale
+ *   done == 0:  M2 = 0, yprev = y                          (the state need not be initialised)
+ *   done  > 0:  mb = (y - yprev) / (float)c                 the mean luminance of this batch
+ *               mp = yprev / (float)done                    the mean of everything before it
+ *               d = mb - mp
+ *               w = ((float)done * (float)c) / (float)(done + c)
+ *               M2 = M2 + (d * d) * w, yprev = y            (Chan et al.'s pairwise update: no sq - n m m cancellation)
+ * Finish, after `batches` folds that covered `samples` samples:  var = max(0, M2 / (float)(batches - 1)) / (float)samples.
+ * With batches of equal size that is the sample variance of the batch means over the number of batches, i.e. an unbiased estimate of
+ * the variance of the pixel's mean with batches - 1 degrees of freedom (relative standard deviation sqrt(2 / (batches - 1)) for
+ * Gaussian noise); with unequal batches the weights w keep it unbiased.  Under HRT_FLAG_STRATIFIED consecutive sample ranges are not
+ * independent and the estimate is too large (conservative).
+ * Adaptive, from the buffers of hrt_render_stripes_adaptive*, per pixel:  n = (float)count, m = Y(sums) / n,
+ *   var = max(0, (sq - n * m * m) / (n - 1.0f)) / n, and var = 0 where count < 2.
+ *
+ * HRT_ERR_INVALID, with a message, for a NULL argument, n_pixels < 1 or > 2^30, samples_before < 0, samples_batch < 1, a sum of the two
+ * above 2^31 - 1, batches < 2, samples < batches, a scale that is not finite and positive, or a misaligned pointer (state: 8 bytes,
+ * everything else: 4) -- decided before any device is touched, and the outputs are left untouched. */
+/* The bytes of the state of n_pixels pixels (8 per pixel); 0 when n_pixels is below 1 or above 2^30. */
+uint64_t hrt_variance_state_bytes(int64_t n_pixels);
+/* Asynchronous, on HIP stream `stream` of `device`, DEVICE buffers: one fold. */
+hrt_status hrt_variance_fold_device(int device, int64_t n_pixels, const float* d_rgb, float scale, int32_t samples_before,
+                                    int32_t samples_batch, float* d_state, void* stream);
+/* Asynchronous: the variance (1 float per pixel) from the state. */
+hrt_status hrt_variance_finish_device(int device, int64_t n_pixels, const float* d_state, int32_t samples, int32_t batches, float* d_var,
+                                      void* stream);
+/* Asynchronous: the variance from the buffers of an adaptive render. */
+hrt_status hrt_adaptive_variance_device(int device, int64_t n_pixels, const float* d_sums, const float* d_sq, const int32_t* d_count,
+                                        float* d_var, void* stream);
+/* Blocking, HOST buffers: `state` is uploaded first when samples_before > 0, and downloaded after the fold.  The same refusals. */
+hrt_status hrt_variance_fold(int device, int64_t n_pixels, const float* rgb, float scale, int32_t samples_before, int32_t samples_batch,
+                             float* state);
+hrt_status hrt_variance_finish(int device, int64_t n_pixels, const float* state, int32_t samples, int32_t batches, float* var);
+hrt_status hrt_adaptive_variance(int device, int64_t n_pixels, const float* sums, const float* sq, const int32_t* count, float* var);
+
 /* ---- multi-GPU session -----------------------------------
  * The reference's render() (main.cpp:81-140) has one parallel loop over all pixels of the film (main.cpp:111-135, no state
  * shared between pixels).  Here the flattened scene is replicated on `n_devices` GPUs of THIS process (`devices` = their
