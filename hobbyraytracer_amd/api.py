@@ -147,6 +147,7 @@ HIP_SYMBOLS = ["hrt_device_count", "hrt_scene_create", "hrt_scene_destroy", "hrt
                "hrt_render_stripes_adaptive_device", "hrt_render_stripes_adaptive", "hrt_adaptive_mean_device", "hrt_env_table_build",
                "hrt_emitter_table_build", "hrt_scene_set_roulette", "hrt_multi_set_roulette",
                "hrt_render_aov_tile", "hrt_render_aov_stripes_device", "hrt_render_aov_stripes",
+               "hrt_aov_ids_bytes", "hrt_render_aov_ids_tile", "hrt_render_aov_ids_stripes_device", "hrt_render_aov_ids_stripes",
                "hrt_denoise_defaults", "hrt_denoise_workspace_bytes", "hrt_denoise_device", "hrt_denoise", "hrt_denoise_resolve_u8",
                "hrt_variance_state_bytes", "hrt_variance_fold_device", "hrt_variance_finish_device", "hrt_adaptive_variance_device",
                "hrt_variance_fold", "hrt_variance_finish", "hrt_adaptive_variance"]
@@ -210,6 +211,11 @@ _hip.hrt_multi_set_roulette.argtypes = [_vp, C.c_int32, C.c_float]
 _hip.hrt_render_aov_tile.argtypes = [_vp, C.POINTER(Camera), C.POINTER(Params), Rect, _fp]
 _hip.hrt_render_aov_stripes_device.argtypes = [_vp, C.POINTER(Camera), C.POINTER(Params), C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32, _vp]
 _hip.hrt_render_aov_stripes.argtypes = [_vp, C.POINTER(Camera), C.POINTER(Params), C.c_int32, C.c_int32, C.c_int32, _fp, C.c_int32, C.c_int32]
+_hip.hrt_aov_ids_bytes.argtypes = [C.c_int64]
+_hip.hrt_aov_ids_bytes.restype = C.c_uint64
+_hip.hrt_render_aov_ids_tile.argtypes = [_vp, C.POINTER(Camera), C.POINTER(Params), Rect, _vp]
+_hip.hrt_render_aov_ids_stripes_device.argtypes = [_vp, C.POINTER(Camera), C.POINTER(Params), C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32, _vp]
+_hip.hrt_render_aov_ids_stripes.argtypes = [_vp, C.POINTER(Camera), C.POINTER(Params), C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, C.c_int32]
 _hip.hrt_denoise_defaults.argtypes = [C.POINTER(DenoiseParams)]
 _hip.hrt_denoise_defaults.restype = None
 _hip.hrt_denoise_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
@@ -501,6 +507,40 @@ def split_aov(buf):
     if buf.shape[-1] != 8:
         raise ValueError("a feature buffer has 8 floats per pixel")
     return {"albedo": buf[..., 0:3], "alpha": buf[..., 3], "normal": buf[..., 4:7], "depth": buf[..., 7]}
+
+
+# One pixel of the buffer of hrt_render_aov_ids_* (include/hrt.h): 80 bytes, five groups of 16.
+AOV_IDS_DTYPE = np.dtype([("position", "<f4", 4), ("object_id", "<i4", 4), ("object_coverage", "<f4", 4), ("material_id", "<i4", 4),
+                          ("material_coverage", "<f4", 4)])
+assert AOV_IDS_DTYPE.itemsize == 80
+AOV_ID_SLOTS, AOV_ID_RANKS = 8, 4
+AOV_ID_UNUSED = -2 ** 31       # the id of a rank beyond the used slots (INT32_MIN); its coverage is +0
+
+
+def aov_ids_bytes(n_pixels):
+    return int(_hip.hrt_aov_ids_bytes(n_pixels))
+
+
+def split_aov_ids(buf):
+    """A raw id buffer [...] of AOV_IDS_DTYPE (hrt_render_aov_ids_*) as a dict of views: position [..., 3] fp32, object_id [..., 4]
+    int32, object_coverage [..., 4] fp32, material_id [..., 4] int32, material_coverage [..., 4] fp32; rank 0 first."""
+    if buf.dtype != AOV_IDS_DTYPE:
+        raise ValueError("an id buffer has dtype AOV_IDS_DTYPE (80 bytes per pixel)")
+    return {"position": buf["position"][..., 0:3], "object_id": buf["object_id"], "object_coverage": buf["object_coverage"],
+            "material_id": buf["material_id"], "material_coverage": buf["material_coverage"]}
+
+
+def matte(ids, coverage, wanted):
+    """The matte of the ids in `wanted` (an int or an iterable of ints): ids [..., 4] int32 and coverage [..., 4] fp32 of one id kind
+    (split_aov_ids) -> [...] fp32, the sum of the coverages of the ranks whose id is wanted, added in rank order in fp32 from +0."""
+    ids, coverage = np.asarray(ids), np.asarray(coverage, dtype=np.float32)
+    if ids.shape != coverage.shape or ids.shape[-1] != AOV_ID_RANKS:
+        raise ValueError("matte takes ids and coverage of the same shape [..., 4]")
+    wanted = np.atleast_1d(np.asarray(wanted, dtype=np.int64)).ravel()
+    out = np.zeros(ids.shape[:-1], dtype=np.float32)
+    for k in range(AOV_ID_RANKS):
+        out = out + np.where(np.isin(ids[..., k], wanted), coverage[..., k], np.float32(0.0)).astype(np.float32)
+    return out
 
 
 def denoise_defaults(**params):
@@ -817,6 +857,35 @@ class DeviceScene:
         """Asynchronous: d_buf_ptr is a device pointer to rows x W x 8 floats (e.g. a torch tensor's .data_ptr())."""
         _check(_hip.hrt_render_aov_stripes_device(self._h, C.byref(cam), C.byref(params), rows_per_block, rank, n_ranks, _vp(d_buf_ptr),
                                                   sample_first, sample_count, _vp(stream)))
+
+    def render_aov_ids_tile(self, cam, params, rect=None):
+        """The id mattes and the position buffer of a film tile (hrt_render_aov_ids_tile) over samples
+        [0, params.samples) -> a dict: position [h, w, 3] fp32, object_id [h, w, 4] int32, object_coverage [h, w, 4] fp32, material_id,
+        material_coverage (split_aov_ids)."""
+        if rect is None:
+            rect = Rect(0, 0, params.width, params.height)
+        elif not isinstance(rect, Rect):
+            rect = Rect(*rect)
+        out = np.empty((max(rect.h, 0), max(rect.w, 0)), dtype=AOV_IDS_DTYPE)
+        _check(_hip.hrt_render_aov_ids_tile(self._h, C.byref(cam), C.byref(params), rect, _vp(out.ctypes.data)))
+        return split_aov_ids(out)
+
+    def render_aov_ids_stripes(self, cam, params, rows_per_block, rank, n_ranks, buf=None, sample_first=0, sample_count=-1):
+        """Samples [sample_first, sample_first + sample_count) (-1: up to params.samples) of the rank's row blocks into the raw id
+        buffer `buf` ([rows, W] of AOV_IDS_DTYPE, allocated when not given) and returns it (hrt_render_aov_ids_stripes).  Every call
+        starts from empty tables and overwrites the buffer: there is no accumulate form."""
+        rows = stripe_rows(params.height, rows_per_block, rank, n_ranks)
+        if buf is None:
+            buf = np.empty((rows, params.width), dtype=AOV_IDS_DTYPE)
+        assert buf.dtype == AOV_IDS_DTYPE and buf.flags["C_CONTIGUOUS"] and buf.size == rows * params.width
+        _check(_hip.hrt_render_aov_ids_stripes(self._h, C.byref(cam), C.byref(params), rows_per_block, rank, n_ranks, _vp(buf.ctypes.data),
+                                               sample_first, sample_count))
+        return buf
+
+    def render_aov_ids_stripes_device(self, cam, params, rows_per_block, rank, n_ranks, d_buf_ptr, sample_first=0, sample_count=-1, stream=0):
+        """Asynchronous: d_buf_ptr is a device pointer to aov_ids_bytes(rows x W) bytes, 16-byte aligned."""
+        _check(_hip.hrt_render_aov_ids_stripes_device(self._h, C.byref(cam), C.byref(params), rows_per_block, rank, n_ranks, _vp(d_buf_ptr),
+                                                      sample_first, sample_count, _vp(stream)))
 
     def stats(self):
         st = Stats()

@@ -40,41 +40,12 @@
 #include "hrt_pack.h"
 #include "hrt_roulette.h"
 #include "hrt_aov.h"
+#include "hrt_map.h"
 
 using namespace hrt;
 
 // ===================================================================== kernels
 namespace {
-
-struct RenderMap {
-    int32_t mode;            // 0 = rect tile, 1 = interleaved row blocks, 2 = list of row-block pixels (adaptive passes)
-    int32_t x0, y0;          // rect origin
-    int32_t rw, rh;          // local region size
-    int32_t R, rank, G;      // stripes
-    int32_t tiles_x;         // ceil(rw / 8)
-    int32_t total_items;     // tiles_x * ceil(rh / 8) * 64
-    // exact division of 32-bit numbers by rw and by rw*rh as multiply-high + shift (host-computed magic
-    // numbers, fastdiv below): the wavefront kernels turn slot ids into (sample, pixel) for every path
-    uint64_t m_rw, m_nl;
-    // mode 2: local pixel lp of the batch is pixel pix[lp] of the row-block layout (an index in [0, rw * rh), the stripe
-    // order of mode 1); n_list entries, every one of them at the same sample count
-    const int32_t* pix;
-    uint32_t n_list;
-};
-// pixels one render call of `map` covers
-inline uint32_t map_pixels(const RenderMap& map) { return map.mode == 2 ? map.n_list : (uint32_t)map.rw * (uint32_t)map.rh; }
-
-// floor(x / d) for any 32-bit x: with m = floor(2^64 / d) + 1 the product's high half is exact for every
-// x < 2^32 (the error term x / 2^64 * d stays below 1 / d).  d = 1 needs no magic.
-__host__ __device__ inline uint32_t fastdiv(uint32_t x, uint32_t d, uint64_t m) {
-    if (d == 1) return x;
-#if defined(__HIP_DEVICE_COMPILE__)
-    return (uint32_t)__umul64hi(m, (uint64_t)x);
-#else
-    return (uint32_t)(((unsigned __int128)m * x) >> 64);
-#endif
-}
-inline uint64_t fastdiv_magic(uint32_t d) { return d <= 1 ? 0 : (uint64_t)(~0ull / d) + 1; }
 
 // The maps the host renders with (the partitions are validated by the caller).  Rect and stripe maps deal their pixels in
 // 8x8 tiles, the megakernel's work items.
@@ -424,13 +395,6 @@ struct WfScene {                 // world-list split points (host-computed)
     int has_mesh;
 };
 
-__device__ inline void slot_pixel(const RenderMap& map, unsigned lp, int& px, int& py) {
-    if (map.mode == 2) lp = (unsigned)map.pix[lp];   // (uniform branch) the list holds indices of the mode-1 layout
-    const int ly = (int)fastdiv(lp, (unsigned)map.rw, map.m_rw);
-    const int lx = (int)(lp - (unsigned)ly * (unsigned)map.rw);
-    if (map.mode == 0) { px = map.x0 + lx; py = map.y0 + ly; }
-    else { const int b = ly / map.R; px = lx; py = (b * map.G + map.rank) * map.R + (ly - b * map.R); }
-}
 __device__ inline rng_ctx slot_ctx(const hrt_params& pr, const RenderMap& map, unsigned slot, unsigned n_local, int s0, int bounce) {
     int px, py;
     const unsigned sl = fastdiv(slot, n_local, map.m_nl);
@@ -2962,6 +2926,62 @@ hrt_status hrt_render_aov_stripes(hrt_scene* sc, const hrt_camera* cam, const hr
     HRTCHK(check_aov(sc, cam, pr, out, &sample_first, &sample_count));
     HRTCHK(check_stripes(R, rank, G));
     return aov_via_host(sc, cam, pr, stripe_map(pr->width, pr->height, R, rank, G), out, sample_first, sample_count);
+    HRT_API_CATCH
+}
+
+// ---- id mattes and position: k_aov_ids lives in hrt_aov_ids.hip, a unit of its own ----
+extern "C" __attribute__((visibility("hidden"))) hipError_t hrt_aov_ids_launch(const DScene* ds, const hrt_camera* cam, const hrt_params* pr, const void* map,
+                                                                               unsigned n_local, int first, int count, void* d_out, hipStream_t stream);
+namespace {
+hrt_status launch_aov_ids(hrt_scene* sc, const hrt_camera* cam, const hrt_params* pr, const RenderMap& map, void* d_out, int32_t first, int32_t count,
+                          hipStream_t stream) {
+    const unsigned n_local = map_pixels(map);
+    if (n_local == 0) return HRT_OK;
+    if ((uintptr_t)d_out & 15u) return fail(HRT_ERR_INVALID, "id buffer must be 16-byte aligned");
+    HIPCHK(hrt_aov_ids_launch(&sc->ds, cam, pr, &map, n_local, (int)first, (int)count, d_out, stream));
+    return HRT_OK;
+}
+// the host-buffer forms: the pass into device memory of its own, then the copy to `out` (every call overwrites: nothing is copied in)
+hrt_status aov_ids_via_host(hrt_scene* sc, const hrt_camera* cam, const hrt_params* pr, const RenderMap& map, void* out, int32_t first, int32_t count) {
+    const size_t bytes = (size_t)hrt_aov_ids_bytes(map_pixels(map));
+    if (!bytes) return HRT_OK;
+    HIPCHK(hipSetDevice(sc->device));
+    DevBuf buf;
+    HRTCHK(buf.alloc(bytes, "hipMalloc(id buffer)"));
+    HRTCHK(launch_aov_ids(sc, cam, pr, map, buf.get(), first, count, nullptr));
+    HIPCHK(hipMemcpy(out, buf.get(), bytes, hipMemcpyDeviceToHost));
+    return HRT_OK;
+}
+}  // namespace
+
+uint64_t hrt_aov_ids_bytes(int64_t n_pixels) { return n_pixels > 0 ? (uint64_t)n_pixels * 80u : 0; }
+
+hrt_status hrt_render_aov_ids_tile(hrt_scene* sc, const hrt_camera* cam, const hrt_params* pr, hrt_rect tile, void* out) {
+    HRT_API_TRY
+    int32_t first = 0, count = -1;
+    HRTCHK(check_aov(sc, cam, pr, (const float*)out, &first, &count));
+    if (tile.w <= 0 || tile.h <= 0 || tile.x0 < 0 || tile.y0 < 0 || tile.x0 > pr->width - tile.w || tile.y0 > pr->height - tile.h)
+        return fail(HRT_ERR_INVALID, "tile outside the film");
+    return aov_ids_via_host(sc, cam, pr, rect_map(tile), out, first, count);
+    HRT_API_CATCH
+}
+
+hrt_status hrt_render_aov_ids_stripes_device(hrt_scene* sc, const hrt_camera* cam, const hrt_params* pr, int32_t R, int32_t rank, int32_t G,
+                                             void* d_out, int32_t sample_first, int32_t sample_count, void* stream) {
+    HRT_API_TRY
+    HRTCHK(check_aov(sc, cam, pr, (const float*)d_out, &sample_first, &sample_count));
+    HRTCHK(check_stripes(R, rank, G));
+    HIPCHK(hipSetDevice(sc->device));
+    return launch_aov_ids(sc, cam, pr, stripe_map(pr->width, pr->height, R, rank, G), d_out, sample_first, sample_count, (hipStream_t)stream);
+    HRT_API_CATCH
+}
+
+hrt_status hrt_render_aov_ids_stripes(hrt_scene* sc, const hrt_camera* cam, const hrt_params* pr, int32_t R, int32_t rank, int32_t G,
+                                      void* out, int32_t sample_first, int32_t sample_count) {
+    HRT_API_TRY
+    HRTCHK(check_aov(sc, cam, pr, (const float*)out, &sample_first, &sample_count));
+    HRTCHK(check_stripes(R, rank, G));
+    return aov_ids_via_host(sc, cam, pr, stripe_map(pr->width, pr->height, R, rank, G), out, sample_first, sample_count);
     HRT_API_CATCH
 }
 

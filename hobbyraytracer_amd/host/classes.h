@@ -48,6 +48,8 @@ public:
     uint64_t addTexelsU8(const std::vector<uint8_t>& d) { uint64_t o = texels_u8.size(); texels_u8.insert(texels_u8.end(), d.begin(), d.end()); return o; }
     uint64_t addTexelsF32(const std::vector<float>& d) { uint64_t o = texels_f32.size(); texels_f32.insert(texels_f32.end(), d.begin(), d.end()); return o; }
     void setBackground(const std::shared_ptr<Texture>& t) { background = addTexture(t); }
+    // the index addMaterial gave `m`, or -1 when the flattened scene does not hold it
+    int materialId(const Material* m) const { auto it = mat_ids.find(m); return it == mat_ids.end() ? -1 : it->second; }
 
     // the finished scene; pointers stay valid while the builder lives and is not modified
     hrt_flat_scene flat() const;
@@ -382,6 +384,8 @@ public:
     const Camera& getCamera() const { return camera; }
     const std::shared_ptr<Texture>& getBackground() const { return background; }
     const std::shared_ptr<Film>& getFilm() const { return film; }
+    // the scene file's `materials:` entries by name (the id manifest of --aov-ids names the flattened materials after them)
+    const std::map<std::string, std::shared_ptr<Material>>& getMaterials() const { return materials; }
     // rebuilds the camera for an overridden film aspect (CLI --size)
     void setFilmSize(int w, int h, int samples);
     std::string lastError;

@@ -34,6 +34,11 @@
 //         first-hit albedo, normal, depth and coverage of the film's camera rays, for a denoiser or a compositor; depth and alpha in all
 //         three channels.  First device only; depends on --lens, --stratified, --quirks, --seed and --size, on nothing else)
 //     --aov-spp N (the samples per pixel of that pass, samples 0 .. N - 1; min(spp, 16) by default; 1 <= N <= spp; needs --aov or --denoise)
+//     --aov-ids (needs --aov PREFIX; id mattes and position, DESIGN.md 4.14, over the samples of the --aov pass: PREFIX.position.pfm;
+//         PREFIX.object0.pfm .. PREFIX.object3.pfm and PREFIX.material0.pfm .. PREFIX.material3.pfm, the four largest shares of each pixel
+//         with R = the id as a float (-1: no hit; -2147483648: rank unused), G = its coverage, B = 0; PREFIX.ids.txt, what the ids stand for)
+//     --matte object:ID[,ID...] FILE.pfm | --matte material:ID[,ID...] FILE.pfm (the summed coverage of those ids, in all three channels;
+//         may be repeated; implies --aov-ids)
 //     --denoise (the guided denoiser, DESIGN.md 4.12: runs the feature-buffer pass as --aov would -- its files only with --aov PREFIX --
 //         and filters the finished film on the first device with hrt_denoise, spatial variance estimate; the image file and
 //         --dump-linear then hold the filtered film.  Previews and checkpoints stay unfiltered)
@@ -90,6 +95,9 @@ int main(int argc, char** argv) {
     hrt_denoise_params dnp;
     hrt_denoise_defaults(&dnp);
     long aovSpp = -1;
+    bool aovIds = false;
+    struct Matte { bool material; std::vector<int32_t> ids; std::string file; };
+    std::vector<Matte> mattes;
     bool haveAovSpp = false;
     RenderOptions opt;
     int spp = -1, sw = -1, sh = -1;
@@ -162,6 +170,29 @@ int main(int argc, char** argv) {
             if (end == v || *end != '\0' || aovSpp < 1 || aovSpp > 0x7fffffffl) { std::cerr << "--aov-spp takes an integer >= 1" << std::endl; return 2; }
             haveAovSpp = true;
         }
+        else if (a == "--aov-ids") aovIds = true;
+        else if (a == "--matte") {     // object:ID[,ID...] or material:ID[,ID...], then the file
+            const std::string spec = next("--matte");
+            Matte m;
+            const size_t colon = spec.find(':');
+            const std::string kind = spec.substr(0, colon);
+            bool ok = colon != std::string::npos && (kind == "object" || kind == "material");
+            m.material = kind == "material";
+            const char* v = ok ? spec.c_str() + colon + 1 : "";
+            while (ok) {
+                char* end = nullptr;
+                const long id = std::strtol(v, &end, 10);
+                ok = end != v && id >= -1 && id < (1l << 24) && (*end == ',' || *end == '\0');
+                if (!ok) break;
+                m.ids.push_back((int32_t)id);
+                if (*end == '\0') break;
+                v = end + 1;
+            }
+            if (!ok || m.ids.empty()) { std::cerr << "--matte takes object:ID[,ID...] or material:ID[,ID...] (ids from -1, the miss, to 2^24 - 1) and a file" << std::endl; return 2; }
+            m.file = next("--matte");
+            mattes.push_back(m);
+            aovIds = true;
+        }
         else if (a == "--denoise") denoise = true;
         else if (a == "--denoise-iterations") {
             const char* v = next("--denoise-iterations");
@@ -200,6 +231,7 @@ int main(int argc, char** argv) {
         if (opt.pass_samples <= 0) opt.pass_samples = 16;
     } else if (!sampleMap.empty()) { std::cerr << "--sample-map needs --adaptive" << std::endl; return 2; }
     if (haveAovSpp && aovPrefix.empty() && !denoise) { std::cerr << "--aov-spp needs --aov PREFIX" << std::endl; return 2; }
+    if (aovIds && aovPrefix.empty()) { std::cerr << (mattes.empty() ? "--aov-ids" : "--matte") << " needs --aov PREFIX" << std::endl; return 2; }
     if (!dumpNoisy.empty() && !denoise) { std::cerr << "--dump-noisy needs --denoise" << std::endl; return 2; }
     if (!dumpVariance.empty() && !measured) { std::cerr << "--dump-variance needs --denoise-variance measured" << std::endl; return 2; }
     if (!makeAssets.empty()) {
@@ -242,6 +274,15 @@ int main(int argc, char** argv) {
         opt.aov_samples = haveAovSpp ? (int)aovSpp : std::min(film->getFilm().samples, 16);
         opt.aov_out = &aov;
         opt.aov_seconds = &aov_s;
+    }
+    std::vector<uint8_t> aovIdsBuf;
+    std::string idManifest;
+    double aov_ids_s = 0.0;
+    if (aovIds) {
+        opt.aov_ids_out = &aovIdsBuf;
+        opt.aov_ids_seconds = &aov_ids_s;
+        opt.aov_ids_manifest = &idManifest;
+        opt.material_names = &scene.getMaterials();
     }
     std::vector<int32_t> counts;
     if (opt.adaptive >= 0.0f) opt.sample_counts = &counts;
@@ -287,6 +328,42 @@ int main(int argc, char** argv) {
             if (!writePFM(path, img.data(), w, h)) { std::cerr << "cannot write " << path << std::endl; return -1; }
         }
     }
+    if (aovIds) {   // hrt.h's 80 bytes per pixel: position | object ids | object coverages | material ids | material coverages
+        const int w = film->getFilm().width, h = film->getFilm().height;
+        const size_t n = (size_t)w * h;
+        std::vector<float> img(n * 3);
+        auto f32 = [&](size_t i, int word) { float x; std::memcpy(&x, aovIdsBuf.data() + 80 * i + 4 * word, 4); return x; };
+        auto i32 = [&](size_t i, int word) { int32_t x; std::memcpy(&x, aovIdsBuf.data() + 80 * i + 4 * word, 4); return x; };
+        auto write = [&](const std::string& path) {
+            if (writePFM(path, img.data(), w, h)) return true;
+            std::cerr << "cannot write " << path << std::endl;
+            return false;
+        };
+        for (size_t i = 0; i < n; ++i)
+            for (int k = 0; k < 3; ++k) img[3 * i + k] = f32(i, k);
+        if (!write(aovPrefix + ".position.pfm")) return -1;
+        for (int kind = 0; kind < 2; ++kind)
+            for (int rank = 0; rank < HRT_AOV_ID_RANKS; ++rank) {
+                for (size_t i = 0; i < n; ++i) {
+                    img[3 * i] = (float)i32(i, 4 + 8 * kind + rank);
+                    img[3 * i + 1] = f32(i, 8 + 8 * kind + rank);
+                    img[3 * i + 2] = 0.0f;
+                }
+                if (!write(aovPrefix + (kind ? ".material" : ".object") + std::to_string(rank) + ".pfm")) return -1;
+            }
+        for (const Matte& m : mattes) {   // the coverages of the wanted ids, added in rank order
+            for (size_t i = 0; i < n; ++i) {
+                float sum = 0.0f;
+                for (int rank = 0; rank < HRT_AOV_ID_RANKS; ++rank)
+                    if (std::find(m.ids.begin(), m.ids.end(), i32(i, 4 + 8 * (m.material ? 1 : 0) + rank)) != m.ids.end())
+                        sum = sum + f32(i, 8 + 8 * (m.material ? 1 : 0) + rank);
+                img[3 * i] = img[3 * i + 1] = img[3 * i + 2] = sum;
+            }
+            if (!write(m.file)) return -1;
+        }
+        FILE* mf = std::fopen((aovPrefix + ".ids.txt").c_str(), "w");
+        if (!mf || std::fputs(idManifest.c_str(), mf) < 0 || std::fclose(mf) != 0) { std::cerr << "cannot write " << aovPrefix << ".ids.txt" << std::endl; return -1; }
+    }
     if (!sampleMap.empty()) {
         std::vector<float> m(counts.size() * 3);
         for (size_t i = 0; i < counts.size(); ++i) m[3 * i] = m[3 * i + 1] = m[3 * i + 2] = (float)counts[i];
@@ -314,6 +391,10 @@ int main(int argc, char** argv) {
         if (opt.aov_samples > 0) {    // the feature-buffer pass: its samples per pixel and the wall time of the call
             const size_t k = std::strlen(extra);
             std::snprintf(extra + k, sizeof(extra) - k, ", \"aov_spp\": %d, \"aov_s\": %.6f", opt.aov_samples, aov_s);
+        }
+        if (aovIds) {                 // the id pass: the wall time of its call on the feature pass's scene
+            const size_t k = std::strlen(extra);
+            std::snprintf(extra + k, sizeof(extra) - k, ", \"aov_ids_s\": %.6f", aov_ids_s);
         }
         if (denoise) {                // the filter and the resolve of the filtered film: the wall time of the two calls, copies included
             const size_t k = std::strlen(extra);

@@ -18,6 +18,9 @@
 #include <cstdio>
 #include <cstring>
 #include <iostream>
+#include <map>
+#include <sstream>
+#include <string>
 #include <vector>
 
 namespace hrthost {
@@ -188,9 +191,42 @@ hrt_status renderAov(const hrt_flat_scene& flat, const hrt_camera& cam, hrt_para
     if (st != HRT_OK) { std::cerr << "hrt_scene_create: " << hrt_status_str(st) << ": " << hrt_last_error() << std::endl; return st; }
     st = hrt_render_aov_tile(sc, &cam, &pr, hrt_rect{0, 0, pr.width, pr.height}, opt.aov_out->data());
     if (st != HRT_OK) std::cerr << "feature buffers: " << hrt_status_str(st) << ": " << hrt_last_error() << std::endl;
+    double ids_s = 0.0;
+    if (st == HRT_OK && opt.aov_ids_out) {   // the id pass: the same samples, the same scene
+        const auto t1 = std::chrono::high_resolution_clock::now();
+        opt.aov_ids_out->assign((size_t)hrt_aov_ids_bytes((int64_t)pr.width * pr.height), 0);
+        st = hrt_render_aov_ids_tile(sc, &cam, &pr, hrt_rect{0, 0, pr.width, pr.height}, opt.aov_ids_out->data());
+        if (st != HRT_OK) std::cerr << "id mattes: " << hrt_status_str(st) << ": " << hrt_last_error() << std::endl;
+        ids_s = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t1).count();
+        if (opt.aov_ids_seconds) *opt.aov_ids_seconds = ids_s;
+    }
     hrt_scene_destroy(sc);
-    if (opt.aov_seconds) *opt.aov_seconds = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
+    if (opt.aov_seconds) *opt.aov_seconds = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count() - ids_s;
     return st;
+}
+// PREFIX.ids.txt (--aov-ids): what the ids of the mattes stand for, from the flattened scene the pass renders
+std::string idManifest(const FlatBuilder& fb, const std::map<std::string, std::shared_ptr<Material>>* names) {
+    static const char* const primKinds[] = {"sphere", "xy_rect", "xz_rect", "yz_rect", "box", "mesh", "medium", "triangle"};
+    static const char* const matKinds[] = {"lambertian", "metal", "dielectric", "diffuse_light", "isotropic", "pbr", "uv_test"};
+    std::vector<std::string> name(fb.materials.size());
+    if (names)
+        for (const auto& kv : *names) {
+            const int id = fb.materialId(kv.second.get());
+            if (id >= 0 && name[(size_t)id].empty()) name[(size_t)id] = kv.first;
+        }
+    std::ostringstream os;
+    os << "# object ID KIND material MATERIAL_ID | material ID KIND [NAME] | a miss is id -1\n";
+    for (size_t i = 0; i < fb.prims.size(); ++i) {
+        const int k = fb.prims[i].kind;
+        os << "object " << i << " " << (k >= 0 && k < 8 ? primKinds[k] : "unknown") << " material " << fb.prims[i].material << "\n";
+    }
+    for (size_t i = 0; i < fb.materials.size(); ++i) {
+        const int k = fb.materials[i].kind;
+        os << "material " << i << " " << (k >= 0 && k < 7 ? matKinds[k] : "unknown");
+        if (!name[i].empty()) os << " " << name[i];
+        os << "\n";
+    }
+    return os.str();
 }
 }  // namespace
 
@@ -231,6 +267,13 @@ hrt_status render(int /*nThreads*/, const std::shared_ptr<Texture> background, c
                (opt.nee && opt.nee_emitters ? HRT_FLAG_NEE_EMITTERS : 0) | (opt.nee && opt.nee_lobes ? HRT_FLAG_NEE_LOBES : 0) |
                (opt.stratified ? HRT_FLAG_STRATIFIED : 0) | (opt.roulette ? HRT_FLAG_ROULETTE : 0);
 
+    if (opt.aov_samples > 0 && opt.aov_out && opt.aov_ids_out) {
+        if (fb.prims.size() >= (1u << 24) || fb.materials.size() >= (1u << 24)) {
+            std::cerr << "--aov-ids: the scene has 2^24 or more objects or materials; their ids do not fit the float of a PFM file" << std::endl;
+            return HRT_ERR_UNSUPPORTED;
+        }
+        if (opt.aov_ids_manifest) *opt.aov_ids_manifest = idManifest(fb, opt.material_names);
+    }
     if (opt.aov_samples > 0 && opt.aov_out && (st = renderAov(flat, cam, pr, opt)) != HRT_OK) return st;
 
     if (opt.adaptive >= 0.0f) return renderAdaptive(flat, cam, pr, film, opt, stats, render_seconds);

@@ -3,6 +3,7 @@
 #pragma once
 #include <cstdint>
 #include <functional>
+#include <map>
 #include <memory>
 #include <string>
 #include <vector>
@@ -54,6 +55,15 @@ struct RenderOptions {
     int aov_samples = 0;
     std::vector<float>* aov_out = nullptr;
     double* aov_seconds = nullptr;
+    // Id mattes and position (--aov-ids, hrt.h hrt_render_aov_ids_tile): with aov_ids_out set (and aov_samples > 0) the
+    // feature-buffer pass is followed, on its own temporary scene, by the id pass over the same samples; *aov_ids_out gets width *
+    // height * 80 bytes in film order, *aov_ids_seconds (optional) the wall time of that call alone.  *aov_ids_manifest (optional) gets
+    // the text of PREFIX.ids.txt: one line per object id (primitive kind, material id) and one per material id (kind, and the name
+    // `material_names` has for it, when it has one).  Ids of 2^24 or more would not survive the float of the PFM files: refused.
+    std::vector<uint8_t>* aov_ids_out = nullptr;
+    double* aov_ids_seconds = nullptr;
+    std::string* aov_ids_manifest = nullptr;
+    const std::map<std::string, std::shared_ptr<Material>>* material_names = nullptr;
     // Measured variance (--denoise-variance measured, hrt.h hrt_variance_*): with variance_out set the render measures
     // the variance of every pixel's mean luminance -- an adaptive render from its own buffers (hrt_adaptive_variance), any other from
     // the batch means of its passes: the passes of pass_samples or, without them, variance_batches passes (range j starts at

@@ -455,6 +455,54 @@ hrt_status hrt_render_aov_stripes_device(hrt_scene* scene, const hrt_camera* cam
 hrt_status hrt_render_aov_stripes(hrt_scene* scene, const hrt_camera* cam, const hrt_params* params, int32_t rows_per_block, int32_t rank,
                                   int32_t n_ranks, float* out, int32_t sample_first, int32_t sample_count);
 
+/* ---- id mattes and position --------------------------------
+ * What a compositor needs to isolate an object or a material: for every pixel, which objects and which materials its samples saw
+ * first and what share of the samples each of them took, and where the surface is.  Sample s of pixel (px, py) traces exactly the ray
+ * of the feature buffers above -- the film's camera ray under (seed, pixel, s), HRT_FLAG_THIN_LENS, HRT_FLAG_STRATIFIED and
+ * params->quirks, to its first hit; every other flag is accepted and has no effect -- and yields
+ *   object id     hit: the index of the hit primitive in hrt_flat_scene::prims      miss: -1
+ *   material id   hit: the material index of the film's hitRecord there             miss: -1
+ *   position      hit: hitRecord::p, fp32                                           miss: 0, 0, 0
+ *
+ * The matte rule.  A pixel owns, for each of the two id kinds, a table of HRT_AOV_ID_SLOTS (id, count) slots, empty when the call
+ * starts.  The samples of the call are visited in ascending order.  A sample whose id is in the table adds 1 to that slot's count.
+ * Otherwise it takes the first empty slot, with count 1.  Otherwise -- the table is full -- the sample is dropped: its share of the
+ * pixel shows only as 1 - (the sum of the coverages reported).  After the last sample the used slots are ordered by count, largest
+ * first, and among equal counts by id, smallest first (ids are signed: the miss id -1 comes before 0).  The first HRT_AOV_ID_RANKS
+ * slots of that order are reported as id (int32) and coverage = (float)count / (float)sample_count, one IEEE fp32 division; a rank
+ * beyond the used slots is id = INT32_MIN, coverage = +0.
+ *
+ * Position is the plain fp32 sum of the samples' positions in sample order, starting from +0, each component divided once by
+ * (float)sample_count: like the feature buffers it is premultiplied by coverage (misses add 0, 0, 0).
+ *
+ * 80 bytes per pixel, five groups of 16:
+ *   float position x, y, z, 0 | int32 object id of rank 0 .. 3 | float object coverage of rank 0 .. 3 |
+ *   int32 material id of rank 0 .. 3 | float material coverage of rank 0 .. 3
+ * in the pixel order of hrt_render_aov_*: row-major within the tile, or the rank's row blocks.
+ *
+ * There is no accumulate form: a bounded table cannot be continued exactly (whether a dropped sample would have been dropped depends
+ * on every sample before it), so each call takes its sample range, starts from empty tables and overwrites the buffer, whatever
+ * sample_first is.  The pass counts nothing: hrt_stats and hrt_scene_stats do not see it.  Not reported: triangle ids, motion
+ * vectors, hashed names.
+ *
+ * Every entry point returns HRT_ERR_INVALID, with a message, for a NULL argument, an empty tile or one outside the film, a bad
+ * partition, an empty sample range or one outside [0, params->samples), and a device pointer that is not 16-byte aligned; the buffer
+ * is then untouched. */
+#define HRT_AOV_ID_SLOTS 8
+#define HRT_AOV_ID_RANKS 4
+/* bytes of the buffer of n_pixels pixels (80 each); 0 for n_pixels < 0 */
+uint64_t hrt_aov_ids_bytes(int64_t n_pixels);
+/* Blocking: tile (x0,y0,w,h) of the film, samples [0, params->samples), into the caller-owned HOST buffer of hrt_aov_ids_bytes(w*h). */
+hrt_status hrt_render_aov_ids_tile(hrt_scene* scene, const hrt_camera* cam, const hrt_params* params, hrt_rect tile, void* out);
+/* Asynchronous, on HIP stream `stream`: samples [sample_first, sample_first + sample_count) of the row blocks of `rank`
+ * (hrt_render_stripes_device's layout) into a DEVICE buffer of hrt_aov_ids_bytes(hrt_stripe_rows(...) * W), 16-byte aligned.
+ * sample_count < 0 means params->samples - sample_first. */
+hrt_status hrt_render_aov_ids_stripes_device(hrt_scene* scene, const hrt_camera* cam, const hrt_params* params, int32_t rows_per_block,
+                                             int32_t rank, int32_t n_ranks, void* d_out, int32_t sample_first, int32_t sample_count, void* stream);
+/* Blocking host-buffer form of the above. */
+hrt_status hrt_render_aov_ids_stripes(hrt_scene* scene, const hrt_camera* cam, const hrt_params* params, int32_t rows_per_block, int32_t rank,
+                                      int32_t n_ranks, void* out, int32_t sample_first, int32_t sample_count);
+
 /* ---- guided denoiser --------------------------------------
  * An edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) with a variance-guided luminance weight (the spatial part of SVGF,
  * Schied et al. 2017) over albedo-demodulated radiance, guided by the feature buffers above.  It needs no scene.  Everything is fp32 and
