@@ -1450,6 +1450,14 @@ __global__ __launch_bounds__(256, DEPTH <= 24 ? 4 : 3) void k_wf_tail(DScene sc,
     }
 }
 
+// k_wf_merge (hrt_merge.hip, a unit of its own): before k_wf_tail takes a large batch's late rounds over, every K neighbouring tasks
+// become ONE task of K x T positions -- the live state records of parity `par` move to the front of the merged segment, the merged counts
+// go to a second set of per-task arrays (launch_wavefront, DESIGN.md 4.1 "the merged tail").
+#define HRT_MERGE_TASKS_PER_WAVE 1    // F: K is the smallest that leaves at most F merged tasks per resident k_wf_tail wave
+extern "C" __attribute__((visibility("hidden"))) void hrt_wf_merge_launch(float4* s0, float4* s1, float4* s2, float* s3, const unsigned* live, unsigned T,
+                                                                          unsigned n_tasks, unsigned K, unsigned* live_m, unsigned* qn_m, unsigned* rn_m,
+                                                                          hipStream_t stream);
+
 // Per pixel: add the batch's samples IN SAMPLE ORDER (main.cpp:118-124); divide once all samples are in (main.cpp:126).
 // NEE: a sample's value is rad + direct (result + the shadow terms), formed before it is added.
 __device__ inline float4 wf_sample_value(const float4* __restrict__ rad, const float4* __restrict__ direct, size_t i, bool nee) {
@@ -1723,7 +1731,9 @@ struct WfWorkspace {          // device workspace of the wavefront pipeline (gro
     DevBuf base;
     size_t bytes = 0;
     size_t slots = 0;
+    size_t slack = 0;            // positions beyond `slots` in the position-indexed arrays: the largest task of a batch (wf_reserve)
     int depth = 0, n_mesh = 0;
+    unsigned *live_m = nullptr, *qn_m = nullptr, *rn_m = nullptr;   // k_wf_merge: the merged tasks' counts (WfBuf::live / qn / rn of the tail launch)
     bool nee = false;            // holds the HRT_FLAG_NEE buffers (WfBuf::N, direct, wave_shadow)
     bool lobes = false;          // WfBuf::N holds two float4 per position (HRT_FLAG_NEE_LOBES)
     WfBuf buf{};
@@ -2072,18 +2082,20 @@ size_t wf_counter_words(int depth, int n_mesh) { return (size_t)256 * (2 + (size
 // ... and of 512 words per traversal launch for its ref-walk lists (WfBuf::ref_prod / ref_cons), + one block nobody reads
 size_t wf_ref_counter_words(int depth, int n_mesh) { return (size_t)512 * ((size_t)depth * (size_t)std::max(1, n_mesh) + 1); }
 
-hrt_status wf_reserve(hrt_scene* sc, size_t slots, int depth, bool nee, bool lobes) {
+// `slack`: positions beyond `slots`.  The position-indexed arrays reach to a whole number of tasks, because ref-walk records sit at the
+// top of a task's segment: one task of the per-round phase (T <= 4096) or one merged task of k_wf_merge (K x T), whichever is larger.
+hrt_status wf_reserve(hrt_scene* sc, size_t slots, size_t slack, int depth, bool nee, bool lobes) {
     WfWorkspace& w = sc->wf;
     const int n_mesh = (int)sc->mesh_prims.size();
-    if (w.base && w.slots >= slots && w.depth >= depth && w.n_mesh == n_mesh && (w.nee || !nee) && (w.lobes || !lobes)) return HRT_OK;
+    if (w.base && w.slots >= slots && w.slack >= slack && w.depth >= depth && w.n_mesh == n_mesh && (w.nee || !nee) && (w.lobes || !lobes)) return HRT_OK;
     if (w.base) { HIPCHK(hipDeviceSynchronize()); w = WfWorkspace(); }
     const size_t max_tasks = slots / 64 + 1;   // the smallest task HRT_WF_TASK_SIZE can ask for is 64 positions (the default is >= 256)
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t f4 = al((slots + 4096) * sizeof(float4));   // to a whole number of tasks (T <= 4096): ref-walk records sit at the top of a task's segment
-    const size_t i4 = al((slots + 4096) * sizeof(int));
+    const size_t f4 = al((slots + slack) * sizeof(float4));
+    const size_t i4 = al((slots + slack) * sizeof(int));
     const size_t ctr_words = wf_counter_words(depth, n_mesh) + wf_ref_counter_words(depth, n_mesh);
     const size_t ref_cap = max_tasks / HRT_REF_GROUPS + 1;
-    const size_t total = (sc->ds.stale_ff ? 12 : 11) * f4 + 2 * i4 + 3 * al(max_tasks * sizeof(unsigned)) + al(ctr_words * sizeof(unsigned)) + al(ref_cap * HRT_REF_GROUPS * sizeof(uint2)) +
+    const size_t total = (sc->ds.stale_ff ? 12 : 11) * f4 + 2 * i4 + 6 * al(max_tasks * sizeof(unsigned)) + al(ctr_words * sizeof(unsigned)) + al(ref_cap * HRT_REF_GROUPS * sizeof(uint2)) +
                          al((size_t)sc->n_cus * 32 * sizeof(unsigned long long)) +                                     // 184 B per slot
                          (nee ? 3 * f4 + al((size_t)sc->n_cus * 32 * sizeof(unsigned long long)) : 0) +                // + 48 with NEE
                          (lobes ? 2 * f4 : 0);                                                                         // + 32 with NEE_LOBES
@@ -2100,6 +2112,9 @@ hrt_status wf_reserve(hrt_scene* sc, size_t slots, int depth, bool nee, bool lob
     w.buf.live = (unsigned*)take(al(max_tasks * sizeof(unsigned)));
     w.buf.qn = (unsigned*)take(al(max_tasks * sizeof(unsigned)));
     w.buf.rn = (unsigned*)take(al(max_tasks * sizeof(unsigned)));
+    unsigned* const live_m = (unsigned*)take(al(max_tasks * sizeof(unsigned)));
+    unsigned* const qn_m = (unsigned*)take(al(max_tasks * sizeof(unsigned)));
+    unsigned* const rn_m = (unsigned*)take(al(max_tasks * sizeof(unsigned)));
     w.buf.task_ctr = (unsigned*)take(al(ctr_words * sizeof(unsigned)));
     w.buf.ref_list = (uint2*)take(al(ref_cap * HRT_REF_GROUPS * sizeof(uint2)));
     w.buf.ref_cap = (unsigned)ref_cap;
@@ -2111,7 +2126,8 @@ hrt_status wf_reserve(hrt_scene* sc, size_t slots, int depth, bool nee, bool lob
         w.buf.wave_shadow = (unsigned long long*)take(al((size_t)w.buf.n_wave_rays * sizeof(unsigned long long)));
         HIPCHK(hipMemset(w.buf.wave_shadow, 0, (size_t)w.buf.n_wave_rays * sizeof(unsigned long long)));
     }
-    w.base = std::move(base); w.bytes = total; w.slots = slots; w.depth = depth; w.n_mesh = n_mesh; w.nee = nee; w.lobes = lobes;
+    w.live_m = live_m; w.qn_m = qn_m; w.rn_m = rn_m;
+    w.base = std::move(base); w.bytes = total; w.slots = slots; w.slack = slack; w.depth = depth; w.n_mesh = n_mesh; w.nee = nee; w.lobes = lobes;
     return HRT_OK;
 }
 
@@ -2143,11 +2159,73 @@ hrt_status launch_wavefront(hrt_scene* sc, const hrt_camera* cam, const hrt_para
     int chunk = (int)std::min<size_t>((size_t)s_count, std::max<size_t>(1, cap / n_local));
     // (the largest batches that fit plus a remainder, NOT equal batches: C4 on one GPU takes 92.8 ms as 453 + 59 samples and
     //  97.1 ms as 256 + 256 -- a batch's rounds run the better the more paths they hold, round 3)
+    // Task size (positions per task, a multiple of 64).  Large batches: ~64 tasks per CU, so that the strided static
+    // ownership averages over several tasks per wave.  Small batches (one rank's share of a multi-GPU frame): no
+    // more tasks than the ~4096 waves k_wf_shade keeps resident, but up to 1280 positions each -- in the late rounds
+    // a task's survivors then still fill whole 64-lane chunks and a round costs ~2 instead of ~4 dependent chunk
+    // passes (measured on the 1/8 share of the headline frame: 11.4 -> 10.2 ms; tests/tools/stripe_scaling.py).
+    auto round64 = [](size_t x) { return (x + 63) & ~(size_t)63; };
+    auto task_size = [&](size_t n_slots) {
+        const size_t t_large = round64(n_slots / ((size_t)sc->n_cus * 64));
+        const size_t t_small = std::min<size_t>(1280, std::max<size_t>(256, round64(n_slots / ((size_t)sc->n_cus * 16))));
+        size_t T = std::min<size_t>(4096, std::max(t_large, t_small));
+        if (const char* e = getenv("HRT_WF_TASK_SIZE")) T = std::min<size_t>(4096, std::max<size_t>(64, round64((size_t)atoi(e))));   // experiments
+        return T;
+    };
+    // k_wf_tail: the meshes it walks, its stack variant and the waves it keeps resident (38..50 KB of LDS per block)
+    TailMeshes tm{};
+    int tail_variant = 20;
+    if (n_mesh <= HRT_TAIL_MAX_MESHES) {
+        tm.n = n_mesh;
+        int need = 0;
+        for (int m = 0; m < n_mesh; ++m) { tm.prim[m] = sc->mesh_prims[m]; need = std::max(need, sc->mesh_depths[m]); }
+        tail_variant = depth_variant(need);
+    }
+    const size_t tail_blocks_max = (size_t)sc->n_cus * (tail_variant == 32 ? 3 : 4);
+    // The merged tail (k_wf_merge): from round R on, every K neighbouring tasks of a batch run their remaining rounds as
+    // ONE task of k_wf_tail.  K is the smallest that leaves at most HRT_MERGE_TASKS_PER_WAVE merged tasks per resident tail wave; R
+    // follows the merged task's size K x T, i.e. how many paths a tail wave takes over (measured on the headline frame and its 1/2 and
+    // 1/4 shares, merged tasks of 10240 / 5120 / 2560 positions: best from round 28..32 / 20..28 / 12..16, 51.0 -> 49.6, 29.3 -> 27.2
+    // and 17.9 -> 16.5 ms).  Merged by default: batches of more than 6 Mi slots (smaller ones have no more tasks than tail waves)
+    // whose merged tasks fill at least 7/8 of those waves (K = 5 on the headline frame, 3200 tasks on 4096 waves, keeps 0.4 of the
+    // 1.4 ms and loses from round 24; K = 2 or 3, i.e. two tasks one after the other on some waves, keeps 0.5) and are no larger
+    // than the 12288 positions measured; in scenes with at most one mesh (with several, k_wf_tail would prepare round R's further
+    // meshes a second time) and none of the render modes the tail has no stage for.  Every other batch keeps the schedule above.
+    // HRT_WF_MERGE_ROUND = R forces the merge from round R for any batch size ("off" or >= max_depth: never), HRT_WF_MERGE_FACTOR = K
+    // overrides the derived K; HRT_WF_TAIL_ROUND set means the un-merged schedule, as ever.
+    const bool stale_ff = sc->ds.stale_ff && (pr->quirks & HRT_Q3_TRI_NO_FACE);
+    int merge_forced = -1;               // HRT_WF_MERGE_ROUND's round
+    bool merge_off = false;
+    if (const char* e = getenv("HRT_WF_MERGE_ROUND")) {
+        if (!strcmp(e, "off")) merge_off = true;
+        else merge_forced = std::max(0, atoi(e));
+    }
+    size_t merge_factor = 0;
+    if (const char* e = getenv("HRT_WF_MERGE_FACTOR")) merge_factor = (size_t)std::max(0, atoi(e));
+    const bool merge_ok = !merge_off && !getenv("HRT_WF_TAIL_ROUND") && n_mesh <= 1 && !stale_ff && !nee && !strat && !rr;
+    struct MergePlan { unsigned k; int round; };   // k < 2: the batch is not merged
+    auto merge_plan = [&](size_t n_slots) {
+        const MergePlan none{1u, D};
+        if (!merge_ok) return none;
+        const size_t T = task_size(n_slots), n_tasks = (n_slots + T - 1) / T;
+        const size_t waves = tail_blocks_max * 4 * HRT_MERGE_TASKS_PER_WAVE;
+        const size_t k = std::min(n_tasks, merge_factor ? merge_factor : (n_tasks + waves - 1) / waves);
+        if (k < 2) return none;
+        if (merge_forced >= 0) return merge_forced < D ? MergePlan{(unsigned)k, merge_forced} : none;
+        const size_t n_merged = (n_tasks + k - 1) / k, M = k * T;
+        if (n_slots <= ((size_t)6 << 20) || n_merged * 8 < waves * 7 || M > 12288) return none;
+        const int round = M <= 3072 ? 16 : (M <= 6144 ? 24 : 28);
+        return round < D ? MergePlan{(unsigned)k, round} : none;
+    };
+    // the largest task of a batch of n_slots slots: what the position-indexed arrays must hold beyond the slots
+    auto batch_slack = [&](size_t n_slots) { return std::max<size_t>(4096, (size_t)merge_plan(n_slots).k * task_size(n_slots)); };
     hrt_status st;
     for (;;) {   // the memory estimate can be stale (other processes on the device): halve the batch on OOM
         const size_t slots = (size_t)n_local * chunk;
-        if (slots >= ((size_t)1 << 32) - 4096) return fail(HRT_ERR_UNSUPPORTED, "tile too large for 32-bit slot ids");
-        st = wf_reserve(sc, slots, D, nee, lobes);
+        size_t slack = batch_slack(slots);
+        if (s_count % chunk) slack = std::max(slack, batch_slack((size_t)n_local * (size_t)(s_count % chunk)));   // the shorter last batch
+        if (slots >= ((size_t)1 << 32) - slack) return fail(HRT_ERR_UNSUPPORTED, "tile too large for 32-bit slot ids");
+        st = wf_reserve(sc, slots, slack, D, nee, lobes);
         if (st != HRT_ERR_OOM || chunk == 1) break;
         chunk = (chunk + 1) / 2;
     }
@@ -2177,7 +2255,6 @@ hrt_status launch_wavefront(hrt_scene* sc, const hrt_camera* cam, const hrt_para
     int tail_round = batch_slots <= ((size_t)512 << 10) ? 1 : (batch_slots <= ((size_t)6 << 20) ? 8 : (batch_slots <= ((size_t)12 << 20) ? 24 : D));
     if (const char* e = getenv("HRT_WF_TAIL_ROUND")) tail_round = std::max(1, atoi(e));
     if (n_mesh > HRT_TAIL_MAX_MESHES) tail_round = D;
-    const bool stale_ff = sc->ds.stale_ff && (pr->quirks & HRT_Q3_TRI_NO_FACE);
     if (stale_ff) tail_round = D;        // k_wf_tail has no stage for the stale frontFace (k_wf_stale): round by round
     if (nee) tail_round = D;             // ... nor for the light samples (k_wf_shadow)
     if (strat) tail_round = D;           // ... nor the stratified sampler (k_wf_shade_st)
@@ -2190,18 +2267,16 @@ hrt_status launch_wavefront(hrt_scene* sc, const hrt_camera* cam, const hrt_para
     for (int s0 = s_first; s0 < s_end; s0 += chunk) {
         const int c = std::min(chunk, s_end - s0);
         const unsigned n_slots = n_local * (unsigned)c;
-        // Task size (positions per task, a multiple of 64).  Large batches: ~64 tasks per CU, so that the strided static
-        // ownership averages over several tasks per wave.  Small batches (one rank's share of a multi-GPU frame): no
-        // more tasks than the ~4096 waves k_wf_shade keeps resident, but up to 1280 positions each -- in the late rounds
-        // a task's survivors then still fill whole 64-lane chunks and a round costs ~2 instead of ~4 dependent chunk
-        // passes (measured on the 1/8 share of the headline frame: 11.4 -> 10.2 ms; tests/tools/stripe_scaling.py).
-        auto round64 = [](size_t x) { return (x + 63) & ~(size_t)63; };
-        const size_t t_large = round64(n_slots / ((size_t)sc->n_cus * 64));
-        const size_t t_small = std::min<size_t>(1280, std::max<size_t>(256, round64(n_slots / ((size_t)sc->n_cus * 16))));
-        size_t T = std::min<size_t>(4096, std::max(t_large, t_small));
-        if (const char* e = getenv("HRT_WF_TASK_SIZE")) T = std::min<size_t>(4096, std::max<size_t>(64, round64((size_t)atoi(e))));   // experiments
+        const size_t T = task_size(n_slots);
         w.T = (unsigned)T;
         w.n_tasks = (unsigned)((n_slots + T - 1) / T);
+        w.live = sc->wf.buf.live; w.qn = sc->wf.buf.qn; w.rn = sc->wf.buf.rn;   // (the merged tail of the batch before pointed them elsewhere)
+        const MergePlan plan = merge_plan(n_slots);
+        const unsigned merge_by = plan.k;
+        const int merge_round = plan.round;
+        const bool merge = merge_by >= 2;
+        // the rounds that run launch by launch: all of them up to the tail's; merged, also round merge_round's traversal
+        const int per_round_end = merge ? merge_round + 1 : tail_round;
         const int task_blocks = (int)std::min<size_t>(((size_t)w.n_tasks + 3) / 4, (size_t)sc->n_cus * 8);   // 4 waves = 4 tasks per block
         // How many task groups.  Slot = sample x n_local + pixel, so the tasks of one image region recur every P = n_local / T
         // tasks; group g owns the tasks g, g + G, g + 2G, ...: relative to the image its tasks DRIFT by d = (m P mod G, to the nearer
@@ -2253,7 +2328,7 @@ hrt_status launch_wavefront(hrt_scene* sc, const hrt_camera* cam, const hrt_para
         with_bool(stats, [&](auto S) {
             hipLaunchKernelGGL(strat ? k_wf_gen_st<decltype(S)::value> : k_wf_gen<decltype(S)::value>, dim3(task_blocks), dim3(256), 0, stream, sc->ds, *cam, *pr, map, ws, n_local, s0, n_slots, w, sc->d_counters);
         });
-        for (int r = 0; r < tail_round; ++r) {
+        for (int r = 0; r < per_round_end; ++r) {
             const int par = r & 1;
             for (int m = 0; m < n_mesh; ++m) {
                 const int mp = sc->mesh_prims[m];
@@ -2278,6 +2353,7 @@ hrt_status launch_wavefront(hrt_scene* sc, const hrt_camera* cam, const hrt_para
                 }); });
                 if (timing) { HIPCHK(hipEventRecord(eb, stream)); sc->pending_trav.push_back({ea, eb}); }
             }
+            if (merge && r == merge_round) break;   // this round's shading and every later round: k_wf_merge + k_wf_tail, below
             if (stale_ff) {
                 next_counters((unsigned)task_blocks * 4u);
                 hipLaunchKernelGGL(k_wf_stale, dim3(task_blocks), dim3(256), 0, stream, sc->ds, *pr, par, w);
@@ -2336,18 +2412,20 @@ hrt_status launch_wavefront(hrt_scene* sc, const hrt_camera* cam, const hrt_para
             if (progress)   // paths ended so far = earlier batches + this batch's slots - the live ones (w.live, as k_wf_shade left it)
                 hipLaunchKernelGGL(k_wf_progress, dim3(1), dim3(256), 0, stream, w.live, w.n_tasks, sc->progress_base + n_slots, sc->d_progress);
         }
-        if (tail_round < D) {   // the remaining rounds of every task by the wave that pulls it
-            TailMeshes tm{};
-            tm.n = n_mesh;
-            int need = 0;
-            for (int m = 0; m < n_mesh; ++m) { tm.prim[m] = sc->mesh_prims[m]; need = std::max(need, sc->mesh_depths[m]); }
-            const int variant = depth_variant(need);
-            const int tail_blocks = (int)std::min<size_t>(((size_t)w.n_tasks + 3) / 4, (size_t)sc->n_cus * (variant == 32 ? 3 : 4));   // 38..50 KB of LDS per block
+        if (merge) {   // every merge_by neighbouring tasks become one (k_wf_merge): state of parity merge_round & 1, counts into the second set
+            const unsigned n_merged = (w.n_tasks + merge_by - 1) / merge_by;
+            const int mpar = merge_round & 1;
+            hrt_wf_merge_launch(w.S0[mpar], w.S1[mpar], w.S2[mpar], w.S3[mpar], w.live, w.T, w.n_tasks, merge_by, sc->wf.live_m, sc->wf.qn_m, sc->wf.rn_m, stream);
+            w.T *= merge_by; w.n_tasks = n_merged;
+            w.live = sc->wf.live_m; w.qn = sc->wf.qn_m; w.rn = sc->wf.rn_m;
+        }
+        if (merge || tail_round < D) {   // the remaining rounds of every task by the wave that pulls it
+            const int tail_blocks = (int)std::min<size_t>(((size_t)w.n_tasks + 3) / 4, tail_blocks_max);
             next_counters((unsigned)tail_blocks * 4u);
             w.ref_prod = ref_block(D, 0); w.ref_cons = ref_block(D, 0);
-            with_bool(stats, [&](auto S) { with_depth(variant, [&](auto DP) {
+            with_bool(stats, [&](auto S) { with_depth(tail_variant, [&](auto DP) {
                 hipLaunchKernelGGL((k_wf_tail<decltype(S)::value, decltype(DP)::value>), dim3(tail_blocks), dim3(256), 0, stream, sc->ds, *pr, map, ws, tm, n_local, s0,
-                                   tail_round, D, w, sc->d_counters, leaf_num);
+                                   merge ? merge_round : tail_round, D, w, sc->d_counters, leaf_num);
             }); });
         }
         const int rblocks = grid_for(sc, n_local);
