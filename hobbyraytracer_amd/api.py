@@ -130,6 +130,11 @@ class DenoiseParams(C.Structure):
                 ("albedo_floor", C.c_float)]
 
 
+class DespeckleParams(C.Structure):
+    """hrt_despeckle_params: the outlier filter's settings (include/hrt.h); despeckle_defaults() fills them in."""
+    _fields_ = [("radius", C.c_int32), ("rank", C.c_int32), ("ratio", C.c_float), ("gate_z", C.c_float), ("repair_invalid", C.c_int32)]
+
+
 class Hit(C.Structure):
     _fields_ = [("t", C.c_float), ("prim", C.c_int32), ("tri", C.c_int32), ("front_face", C.c_int32), ("p", C.c_float * 3),
                 ("normal", C.c_float * 3), ("u", C.c_float), ("v", C.c_float)]
@@ -150,7 +155,8 @@ HIP_SYMBOLS = ["hrt_device_count", "hrt_scene_create", "hrt_scene_destroy", "hrt
                "hrt_aov_ids_bytes", "hrt_render_aov_ids_tile", "hrt_render_aov_ids_stripes_device", "hrt_render_aov_ids_stripes",
                "hrt_denoise_defaults", "hrt_denoise_workspace_bytes", "hrt_denoise_device", "hrt_denoise", "hrt_denoise_resolve_u8",
                "hrt_variance_state_bytes", "hrt_variance_fold_device", "hrt_variance_finish_device", "hrt_adaptive_variance_device",
-               "hrt_variance_fold", "hrt_variance_finish", "hrt_adaptive_variance"]
+               "hrt_variance_fold", "hrt_variance_finish", "hrt_adaptive_variance",
+               "hrt_despeckle_defaults", "hrt_despeckle_workspace_bytes", "hrt_despeckle_device", "hrt_despeckle"]
 HOST_SYMBOLS = ["hrt_host_load_yaml", "hrt_host_free", "hrt_host_flat", "hrt_host_film", "hrt_host_camera", "hrt_host_bvh_depth",
                 "hrt_default_params", "hrt_asset_write_teapot_obj", "hrt_asset_write_bust_obj", "hrt_asset_write_hall_hdr",
                 "hrt_host_write_image", "hrt_host_read_hdr", "hrt_host_read_png", "hrt_host_read_jpeg", "hrt_host_write_hdr", "hrt_host_write_pfm", "hrt_host_read_pfm", "hrt_host_last_error", "hrt_host_set_bvh_builder"]
@@ -231,6 +237,12 @@ _hip.hrt_adaptive_variance_device.argtypes = [C.c_int, C.c_int64, _vp, _vp, _vp,
 _hip.hrt_variance_fold.argtypes = [C.c_int, C.c_int64, _fp, C.c_float, C.c_int32, C.c_int32, _fp]
 _hip.hrt_variance_finish.argtypes = [C.c_int, C.c_int64, _fp, C.c_int32, C.c_int32, _fp]
 _hip.hrt_adaptive_variance.argtypes = [C.c_int, C.c_int64, _fp, _fp, C.POINTER(C.c_int32), _fp]
+_hip.hrt_despeckle_defaults.argtypes = [C.POINTER(DespeckleParams)]
+_hip.hrt_despeckle_defaults.restype = None
+_hip.hrt_despeckle_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
+_hip.hrt_despeckle_workspace_bytes.restype = C.c_uint64
+_hip.hrt_despeckle_device.argtypes = [C.c_int, C.c_int32, C.c_int32, C.POINTER(DespeckleParams), _vp, _vp, _vp, _vp, _vp, _vp]
+_hip.hrt_despeckle.argtypes = [C.c_int, C.c_int32, C.c_int32, C.POINTER(DespeckleParams), _fp, _fp, _fp, _fp]
 _hip.hrt_math_probe.argtypes = [C.c_int, C.c_int32, C.c_int64, _fp, _fp, _fp]
 _hip.hrt_sampler_probe.argtypes = [C.c_int, C.c_uint64, C.c_int64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
 _hip.hrt_env_table_build.argtypes = [_fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp]
@@ -594,6 +606,52 @@ def denoise_resolve_u8(rgb_linear, device=0):
     out = np.empty(a.shape, dtype=np.uint8)
     _check(_hip.hrt_denoise_resolve_u8(device, _ptr(a), a.size // 3, _ptr(out, _u8p)))
     return out
+
+
+def despeckle_defaults(**params):
+    """hrt_despeckle_defaults, then the given fields (radius, rank, ratio, gate_z, repair_invalid) -> DespeckleParams."""
+    p = DespeckleParams()
+    _hip.hrt_despeckle_defaults(C.byref(p))
+    names = [n for n, _ in DespeckleParams._fields_]
+    for k, v in params.items():
+        if k not in names:
+            raise TypeError(f"hrt_despeckle_params has no field {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def despeckle_workspace_bytes(width, height):
+    return int(_hip.hrt_despeckle_workspace_bytes(width, height))
+
+
+def despeckle(rgb, variance=None, device=0, return_map=False, **params):
+    """The outlier filter (hrt_despeckle, include/hrt.h) on `device`: the linear film rgb [H, W, 3] and, optionally, the
+    variance of every pixel's mean luminance [H, W] (without it the variance gate is off) -> the filtered film [H, W, 3]; with
+    return_map also the map [H, W]: 1 - s for an outlier, -1 for a repaired pixel, 0 elsewhere.  **params: fields of DespeckleParams
+    that differ from the defaults."""
+    rgb = _f32(rgb)
+    if rgb.ndim != 3 or rgb.shape[2] != 3:
+        raise ValueError("despeckle takes rgb [H, W, 3]")
+    H, W = rgb.shape[:2]
+    var = None
+    if variance is not None:
+        var = _f32(variance)
+        if var.shape != (H, W):
+            raise ValueError("variance must be [H, W]")
+    p = despeckle_defaults(**params)
+    out = np.empty_like(rgb)
+    dmap = np.empty((H, W), np.float32) if return_map else None
+    _check(_hip.hrt_despeckle(device, W, H, C.byref(p), _ptr(rgb), _ptr(var) if var is not None else None, _ptr(out),
+                              _ptr(dmap) if dmap is not None else None))
+    return (out, dmap) if return_map else out
+
+
+def despeckle_device(width, height, d_rgb_ptr, d_out_ptr, d_workspace_ptr, d_var_ptr=None, d_map_ptr=None, device=0, stream=0, params=None):
+    """Asynchronous (hrt_despeckle_device): raw device pointers (e.g. torch tensors' .data_ptr()) to rgb [H, W, 3], out [H, W, 3] (not
+    rgb itself), a workspace of despeckle_workspace_bytes(width, height) and, optionally, the variance [H, W] and the map [H, W]."""
+    p = params if params is not None else despeckle_defaults()
+    _check(_hip.hrt_despeckle_device(device, width, height, C.byref(p), _vp(d_rgb_ptr), _vp(d_var_ptr) if d_var_ptr else None, _vp(d_out_ptr),
+                                     _vp(d_map_ptr) if d_map_ptr else None, _vp(d_workspace_ptr), _vp(stream)))
 
 
 def variance_state_bytes(n_pixels):

@@ -43,7 +43,7 @@
 //         and filters the finished film on the first device with hrt_denoise, spatial variance estimate; the image file and
 //         --dump-linear then hold the filtered film.  Previews and checkpoints stay unfiltered)
 //     --denoise-iterations N (1 .. 8)   --denoise-sigma-l X   --denoise-sigma-z X (finite, > 0; each implies --denoise)
-//     --dump-noisy FILE.pfm (with --denoise: the unfiltered linear film)
+//     --dump-noisy FILE.pfm (with --denoise or --despeckle: the unfiltered linear film)
 //     --denoise-variance spatial|measured (implies --denoise; DESIGN.md 4.13.  spatial, the default: the filter estimates the variance
 //         from a 7 x 7 window.  measured: it is given the variance of every pixel's mean luminance -- with --adaptive from the adaptive
 //         render's buffers, otherwise from the batch means of the render's passes: the passes of --progressive N or, without it,
@@ -53,6 +53,14 @@
 //         the batches are not independent and the measured variance is too large: the filter smooths more)
 //     --denoise-batches K (2 .. 64, default 4, reduced to the samples per pixel; implies --denoise-variance measured)
 //     --dump-variance FILE.pfm (with --denoise-variance measured: the variance in all three channels)
+//     --despeckle (the energy-preserving outlier filter, DESIGN.md 4.15: the finished film goes through hrt_despeckle on the first device
+//         before --denoise, or on its own; the image file and --dump-linear hold the result, --dump-noisy the film before both stages.
+//         It is given the measured variance when the run has one (--denoise-variance measured, --adaptive); without one its variance gate is off and
+//         the program says so.  The denoiser receives the variance unchanged.  Previews and checkpoints stay unfiltered)
+//     --despeckle-ratio X (finite, > 1; 2)   --despeckle-rank K (1 .. 4; 2)   --despeckle-radius R (1 or 2; 1)
+//     --despeckle-gate Z (finite, >= 0; 2; 0 switches the gate off)   (each implies --despeckle)
+//     --despeckle-map FILE.pfm (needs --despeckle: 1 - s where a pixel was brought down to a share s of itself, -1 where a non-finite
+//         pixel was repaired, 0 elsewhere; in all three channels)
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -89,7 +97,10 @@ static void printElapsed(const char* what, std::chrono::high_resolution_clock::t
 int main(int argc, char** argv) {
     auto start = std::chrono::high_resolution_clock::now();
     std::string file = "teapot_scene.yaml";  // main.cpp:146
-    std::string assets, out, makeAssets, dumpLinear, dumpNoisy, sampleMap, aovPrefix, dumpVariance;
+    std::string assets, out, makeAssets, dumpLinear, dumpNoisy, sampleMap, aovPrefix, dumpVariance, despeckleMap;
+    bool despeckle = false;
+    hrt_despeckle_params dsp;
+    hrt_despeckle_defaults(&dsp);
     bool denoise = false, measured = false, haveVarianceMode = false, haveSigmaL = false;
     long denoiseBatches = 4;
     hrt_denoise_params dnp;
@@ -220,6 +231,26 @@ int main(int argc, char** argv) {
             denoise = true;
             if (!haveVarianceMode) measured = true;
         }
+        else if (a == "--despeckle") despeckle = true;
+        else if (a == "--despeckle-rank" || a == "--despeckle-radius") {
+            const bool isRank = a == "--despeckle-rank";
+            const char* v = next(a.c_str());
+            char* end = nullptr;
+            const long n = std::strtol(v, &end, 10);
+            if (end == v || *end != '\0' || n < 1 || n > (isRank ? 4 : 2)) { std::cerr << a << " takes an integer from 1 to " << (isRank ? 4 : 2) << std::endl; return 2; }
+            despeckle = true; (isRank ? dsp.rank : dsp.radius) = (int32_t)n;
+        }
+        else if (a == "--despeckle-ratio") {
+            const float x = number("--despeckle-ratio", next("--despeckle-ratio"));
+            if (!(x > 1.0f) || !std::isfinite(x)) { std::cerr << "--despeckle-ratio takes a finite number > 1" << std::endl; return 2; }
+            despeckle = true; dsp.ratio = x;
+        }
+        else if (a == "--despeckle-gate") {
+            const float x = number("--despeckle-gate", next("--despeckle-gate"));
+            if (!std::isfinite(x)) { std::cerr << "--despeckle-gate takes a finite number >= 0" << std::endl; return 2; }
+            despeckle = true; dsp.gate_z = x;
+        }
+        else if (a == "--despeckle-map") despeckleMap = next("--despeckle-map");
         else if (a == "--dump-variance") dumpVariance = next("--dump-variance");
         else if (a == "--dump-noisy") dumpNoisy = next("--dump-noisy");
         else if (!haveFile) { file = a; haveFile = true; }
@@ -232,7 +263,8 @@ int main(int argc, char** argv) {
     } else if (!sampleMap.empty()) { std::cerr << "--sample-map needs --adaptive" << std::endl; return 2; }
     if (haveAovSpp && aovPrefix.empty() && !denoise) { std::cerr << "--aov-spp needs --aov PREFIX" << std::endl; return 2; }
     if (aovIds && aovPrefix.empty()) { std::cerr << (mattes.empty() ? "--aov-ids" : "--matte") << " needs --aov PREFIX" << std::endl; return 2; }
-    if (!dumpNoisy.empty() && !denoise) { std::cerr << "--dump-noisy needs --denoise" << std::endl; return 2; }
+    if (!dumpNoisy.empty() && !denoise && !despeckle) { std::cerr << "--dump-noisy needs --denoise or --despeckle" << std::endl; return 2; }
+    if (!despeckleMap.empty() && !despeckle) { std::cerr << "--despeckle-map needs --despeckle" << std::endl; return 2; }
     if (!dumpVariance.empty() && !measured) { std::cerr << "--dump-variance needs --denoise-variance measured" << std::endl; return 2; }
     if (!makeAssets.empty()) {
         long t = writeTeapotObj(makeAssets + "/teapot.obj", 1.0);
@@ -263,9 +295,10 @@ int main(int argc, char** argv) {
     if (opt.adaptive >= 0.0f && film->getFilm().samples < 2) { std::cerr << "--adaptive needs at least 2 samples per pixel" << std::endl; return 2; }
     if (haveAovSpp && aovSpp > film->getFilm().samples) { std::cerr << "--aov-spp must not exceed the samples per pixel (" << film->getFilm().samples << ")" << std::endl; return 2; }
     std::vector<float> aov;
-    double aov_s = 0.0, denoise_s = 0.0, variance_s = 0.0;
+    double aov_s = 0.0, denoise_s = 0.0, variance_s = 0.0, despeckle_s = 0.0;
+    unsigned long long despecklePixels = 0, despeckleRepaired = 0;
     std::vector<float> variance;
-    if (measured) {
+    if (measured || (despeckle && opt.adaptive >= 0.0f)) {   // (an adaptive render's buffers hold a variance: the outlier filter takes it)
         opt.variance_out = &variance;
         opt.variance_seconds = &variance_s;
         opt.variance_batches = (int)denoiseBatches;
@@ -292,6 +325,26 @@ int main(int argc, char** argv) {
     hrt_status st = render(NUM_THREADS, background, world, camera, film, opt, &stats, &seconds);
     if (st != HRT_OK) return -1;
 
+    std::vector<float> unfiltered;   // the film before both stages, for --dump-noisy
+    if (despeckle || denoise) unfiltered = film->linear();
+    if (despeckle) {   // the finished film through the outlier filter on the first device, ahead of the denoiser; resolved below unless --denoise does
+        const int w = film->getFilm().width, h = film->getFilm().height;
+        const auto t0 = std::chrono::high_resolution_clock::now();
+        const bool haveVariance = variance.size() == (size_t)w * h;
+        if (!haveVariance && dsp.gate_z > 0.0f) std::cerr << "despeckle: no measured variance (--denoise-variance measured, --adaptive): the variance gate is off" << std::endl;
+        std::vector<float> map((size_t)w * h);
+        st = hrt_despeckle(0, w, h, &dsp, unfiltered.data(), haveVariance ? variance.data() : nullptr, film->linear().data(), map.data());
+        if (st == HRT_OK && !denoise) st = hrt_denoise_resolve_u8(0, film->linear().data(), (int64_t)w * h, film->getPixels());
+        if (st != HRT_OK) { std::cerr << "despeckle: " << hrt_status_str(st) << ": " << hrt_last_error() << std::endl; return -1; }
+        despeckle_s = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
+        for (const float m : map) { despecklePixels += m > 0.0f; despeckleRepaired += m < 0.0f; }
+        if (!despeckleMap.empty()) {
+            std::vector<float> img((size_t)w * h * 3);
+            for (size_t i = 0; i < (size_t)w * h; ++i) img[3 * i] = img[3 * i + 1] = img[3 * i + 2] = map[i];
+            if (!writePFM(despeckleMap, img.data(), w, h)) { std::cerr << "cannot write " << despeckleMap << std::endl; return -1; }
+        }
+        if (!denoise && !dumpNoisy.empty() && !writePFM(dumpNoisy, unfiltered.data(), w, h)) { std::cerr << "cannot write " << dumpNoisy << std::endl; return -1; }
+    }
     if (denoise) {   // the finished film, filtered on the first device and resolved as the film resolves itself; the noisy one is kept for --dump-noisy
         const int w = film->getFilm().width, h = film->getFilm().height;
         const auto t0 = std::chrono::high_resolution_clock::now();
@@ -303,7 +356,7 @@ int main(int argc, char** argv) {
         if (st == HRT_OK) st = hrt_denoise_resolve_u8(0, film->linear().data(), (int64_t)w * h, film->getPixels());
         if (st != HRT_OK) { std::cerr << "denoise: " << hrt_status_str(st) << ": " << hrt_last_error() << std::endl; return -1; }
         denoise_s = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
-        if (!dumpNoisy.empty() && !writePFM(dumpNoisy, noisy.data(), w, h)) { std::cerr << "cannot write " << dumpNoisy << std::endl; return -1; }
+        if (!dumpNoisy.empty() && !writePFM(dumpNoisy, unfiltered.data(), w, h)) { std::cerr << "cannot write " << dumpNoisy << std::endl; return -1; }
         if (!dumpVariance.empty() && !haveVariance) std::cerr << "--dump-variance: no variance was measured, " << dumpVariance << " is not written" << std::endl;
         if (!dumpVariance.empty() && haveVariance) {
             std::vector<float> img((size_t)w * h * 3);
@@ -378,7 +431,7 @@ int main(int argc, char** argv) {
                              12.0 * film->getFilm().width * film->getFilm().height;
         // wall_s: the reference's own stopwatch (main.cpp:144,184): process start to after the image file is written
         const double wall_s = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - start).count();
-        char extra[384] = "";
+        char extra[512] = "";
         if (opt.adaptive >= 0.0f) {   // the samples adaptive sampling took, and their share of the uniform render's
             const double uniform = (double)film->getFilm().width * film->getFilm().height * film->getFilm().samples;
             std::snprintf(extra, sizeof(extra), ", \"adaptive_threshold\": %g, \"samples_taken\": %llu, \"sample_fraction\": %.6f",
@@ -399,6 +452,10 @@ int main(int argc, char** argv) {
         if (denoise) {                // the filter and the resolve of the filtered film: the wall time of the two calls, copies included
             const size_t k = std::strlen(extra);
             std::snprintf(extra + k, sizeof(extra) - k, ", \"denoise_s\": %.6f", denoise_s);
+        }
+        if (despeckle) {              // the outlier filter (and, without --denoise, the resolve): the wall time, copies included; the counts from its map
+            const size_t k = std::strlen(extra);
+            std::snprintf(extra + k, sizeof(extra) - k, ", \"despeckle_s\": %.6f, \"despeckle_pixels\": %llu, \"despeckle_repaired\": %llu", despeckle_s, despecklePixels, despeckleRepaired);
         }
         if (measured) {               // the measured variance: the wall time of its folds on the first device, copies included
             const size_t k = std::strlen(extra);

@@ -614,6 +614,59 @@ hrt_status hrt_variance_fold(int device, int64_t n_pixels, const float* rgb, flo
 hrt_status hrt_variance_finish(int device, int64_t n_pixels, const float* state, int32_t samples, int32_t batches, float* var);
 hrt_status hrt_adaptive_variance(int device, int64_t n_pixels, const float* sums, const float* sq, const int32_t* count, float* var);
 
+/* ---- despeckle --------------------------------------------
+ * An energy-preserving outlier filter for the film ahead of the denoiser.  A pixel far brighter than its window (a "firefly") is brought
+ * down to a yardstick taken from the window, and what it held above the yardstick is dealt out in equal shares over the window's valid
+ * pixels, itself included, so that no energy leaves the film; a pixel with a non-finite channel becomes the mean of its valid
+ * neighbours.  It needs no scene.  Everything is fp32 and uses only + - * /, sqrtf and comparisons, evaluated in the order written here
+ * without fused multiply-adds, so that a restatement of these words with IEEE fp32 operations gives the same bits
+ * (tests/despeckle_np.py).  Y is the luminance of the denoiser's text above; max(0, x) means (x > 0 ? x : 0): a NaN gives 0.
+ *
+ * Inputs, whole-film images in film order (row 0 = top), W x H pixels:
+ *   rgb   3 floats per pixel: the film's linear means c
+ *   var   optional (NULL: the gate of step 3 is off), 1 float per pixel: the variance of the pixel's mean luminance, as
+ *         hrt_variance_finish or hrt_adaptive_variance give it
+ * The window of a pixel p is the (2 * radius + 1) x (2 * radius + 1) square around it; only its pixels inside the film count.
+ *
+ * 1. Validity and luminance, per pixel:  l = Y(c).  A pixel is valid when c.r, c.g, c.b and l are all finite.
+ * 2. Yardstick, per valid pixel p:  of the luminances of the valid pixels of p's window, p itself left out, ref is the rank-th largest
+ *    (equal values are separate entries).  With fewer than `rank` such pixels p is not an outlier.
+ * 3. Outlier test:  p is an outlier when it is valid and l > 0 and ref >= 0 and l > ratio * ref and, when var is given and gate_z > 0,
+ *    gate_z * sqrtf(max(0, var_p)) >= l - ref.  (A single-sample spike of value x among n samples has an excess and a standard
+ *    deviation of its mean that are both about x / n and passes the gate; a real highlight has a small variance and is left alone.)
+ * 4. Kept part and shares, per outlier:  s = ref / l,  kept_k = c_k * s,  excess_k = c_k - kept_k,  share_k = excess_k / (float)n with
+ *    n the number of valid pixels of its window, itself included.  For every other pixel kept = c and share = 0.
+ * 5. Output:
+ *    a valid p:  out_k = kept_k, then out_k = out_k + share_q,k for every valid q of p's window, p included, in row-major order
+ *                (dy outer, dx inner); the zero shares of pixels that are no outliers are added like any other.
+ *    an invalid p, with repair_invalid set and at least one valid pixel in its window:  the mean of those pixels' INPUT values,
+ *                sum_k = +0.0f, sum_k = sum_k + c_q,k in row-major order, out_k = sum_k / (float)count.
+ *    any other invalid p keeps its bits.  An invalid pixel receives no share and is never counted in an n.
+ * 6. Map, an optional output of 1 float per pixel:  1.0f - s for an outlier, -1.0f for a repaired pixel, 0 for every other one.
+ *
+ * Every read is of the input image: one pass, no iteration, and the output must not be the input.  Iteration, a robust estimate over
+ * batches and filtering per stripe inside the multi-GPU session are not part of it. */
+typedef struct hrt_despeckle_params {
+    int32_t radius;         /* 1 or 2; default 1: the window is (2 * radius + 1) squared */
+    int32_t rank;           /* 1 .. 4; default 2: the yardstick is the rank-th largest neighbour, so clusters of up to rank - 1 ... */
+    float ratio;            /* finite, > 1; default 2: ... pixels more than `ratio` times brighter than it are outliers */
+    float gate_z;           /* finite, >= 0; default 2: with a variance, the excess must lie within gate_z standard deviations; 0: no gate */
+    int32_t repair_invalid; /* 0 or 1; default 1: a pixel with a non-finite channel becomes the mean of its valid neighbours */
+} hrt_despeckle_params;
+/* Fills in the defaults. */
+void hrt_despeckle_defaults(hrt_despeckle_params* params);
+/* The bytes hrt_despeckle_device needs as workspace for a W x H film (20 per pixel); 0 when W or H is below 1 or W x H above 2^30. */
+uint64_t hrt_despeckle_workspace_bytes(int32_t W, int32_t H);
+/* Asynchronous, on HIP stream `stream` of `device`: filters the DEVICE image d_rgb into d_out; no two buffers may overlap.  d_var and
+ * d_map may be NULL.  d_workspace must be 16-byte aligned.  HRT_ERR_INVALID, with a message, for a NULL required argument, W or H
+ * below 1, more than 2^30 pixels, a parameter outside its range or NaN, d_out == d_rgb, or a misaligned pointer -- decided before any
+ * device is touched, and the outputs are left untouched. */
+hrt_status hrt_despeckle_device(int device, int32_t W, int32_t H, const hrt_despeckle_params* params, const float* d_rgb, const float* d_var,
+                                float* d_out, float* d_map, void* d_workspace, void* stream);
+/* Blocking, HOST buffers; var and map may be NULL; allocates its own workspace on `device`.  The same refusals. */
+hrt_status hrt_despeckle(int device, int32_t W, int32_t H, const hrt_despeckle_params* params, const float* rgb, const float* var,
+                         float* out, float* map);
+
 /* ---- multi-GPU session -----------------------------------
  * The reference's render() (main.cpp:81-140) has one parallel loop over all pixels of the film (main.cpp:111-135, no state
  * shared between pixels).  Here the flattened scene is replicated on `n_devices` GPUs of THIS process (`devices` = their
