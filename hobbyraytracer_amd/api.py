@@ -38,6 +38,10 @@ FLAG_NEE_LOBES = 256
 FLAG_STRATIFIED = 512
 FLAG_ROULETTE = 1024
 ROULETTE_FIRST_BOUNCE, ROULETTE_Q_FLOOR = 3, 0.05   # what a new scene has (hrt_scene_set_roulette)
+FLAG_FILTER = 2048
+FILTER_TENT, FILTER_BSPLINE, FILTER_MITCHELL = 0, 1, 2
+FILTER_KINDS = {"tent": FILTER_TENT, "bspline": FILTER_BSPLINE, "mitchell": FILTER_MITCHELL}
+FILTER_DEFAULT_RADIUS = {FILTER_TENT: 1.0, FILTER_BSPLINE: 2.0, FILTER_MITCHELL: 2.0}   # a new scene has Mitchell at 2 (hrt_scene_set_filter)
 
 
 # ---------------------------------------------------------------- structs (hrt.h)
@@ -156,7 +160,8 @@ HIP_SYMBOLS = ["hrt_device_count", "hrt_scene_create", "hrt_scene_destroy", "hrt
                "hrt_denoise_defaults", "hrt_denoise_workspace_bytes", "hrt_denoise_device", "hrt_denoise", "hrt_denoise_resolve_u8",
                "hrt_variance_state_bytes", "hrt_variance_fold_device", "hrt_variance_finish_device", "hrt_adaptive_variance_device",
                "hrt_variance_fold", "hrt_variance_finish", "hrt_adaptive_variance",
-               "hrt_despeckle_defaults", "hrt_despeckle_workspace_bytes", "hrt_despeckle_device", "hrt_despeckle"]
+               "hrt_despeckle_defaults", "hrt_despeckle_workspace_bytes", "hrt_despeckle_device", "hrt_despeckle",
+               "hrt_scene_set_filter", "hrt_multi_set_filter", "hrt_filter_samples", "hrt_scene_filter_ms", "hrt_multi_filter_ms"]
 HOST_SYMBOLS = ["hrt_host_load_yaml", "hrt_host_free", "hrt_host_flat", "hrt_host_film", "hrt_host_camera", "hrt_host_bvh_depth",
                 "hrt_default_params", "hrt_asset_write_teapot_obj", "hrt_asset_write_bust_obj", "hrt_asset_write_hall_hdr",
                 "hrt_host_write_image", "hrt_host_read_hdr", "hrt_host_read_png", "hrt_host_read_jpeg", "hrt_host_write_hdr", "hrt_host_write_pfm", "hrt_host_read_pfm", "hrt_host_last_error", "hrt_host_set_bvh_builder"]
@@ -243,6 +248,11 @@ _hip.hrt_despeckle_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
 _hip.hrt_despeckle_workspace_bytes.restype = C.c_uint64
 _hip.hrt_despeckle_device.argtypes = [C.c_int, C.c_int32, C.c_int32, C.POINTER(DespeckleParams), _vp, _vp, _vp, _vp, _vp, _vp]
 _hip.hrt_despeckle.argtypes = [C.c_int, C.c_int32, C.c_int32, C.POINTER(DespeckleParams), _fp, _fp, _fp, _fp]
+_hip.hrt_scene_set_filter.argtypes = [_vp, C.c_int32, C.c_float]
+_hip.hrt_multi_set_filter.argtypes = [_vp, C.c_int32, C.c_float]
+_hip.hrt_scene_filter_ms.argtypes = [_vp, C.POINTER(C.c_double)]
+_hip.hrt_multi_filter_ms.argtypes = [_vp, C.POINTER(C.c_double)]
+_hip.hrt_filter_samples.argtypes = [C.c_int, C.c_int32, C.c_float, C.c_int32, C.c_int32, Rect, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, _fp, _fp]
 _hip.hrt_math_probe.argtypes = [C.c_int, C.c_int32, C.c_int64, _fp, _fp, _fp]
 _hip.hrt_sampler_probe.argtypes = [C.c_int, C.c_uint64, C.c_int64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
 _hip.hrt_env_table_build.argtypes = [_fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp]
@@ -295,7 +305,7 @@ def _ptr(a, t=_fp):
 # ---------------------------------------------------------------- host side
 def default_params(width, height, samples, quirks=QUIRKS_REFERENCE, seed=0, max_depth=50, stats=False, megakernel=False, timing=False,
                    thin_lens=False, progress=False, nee=False, nee_env=False, nee_emitters=False, nee_lobes=False, stratified=False,
-                   roulette=False):
+                   roulette=False, filter=False):
     """nee: next-event estimation with MIS for the scene's rect and sphere lights (FLAG_NEE).
     nee_env: also importance-sample the environment map (FLAG_NEE_ENV); implies nee.
     nee_emitters: sample every rect, box and mesh emitter, wrapped or not, by an alias table (FLAG_NEE_EMITTERS, DESIGN.md 4.7);
@@ -304,7 +314,9 @@ def default_params(width, height, samples, quirks=QUIRKS_REFERENCE, seed=0, max_
     stratified: the samples of a pixel from Owen-scrambled (0,2)-sequences instead of independent Philox words (FLAG_STRATIFIED,
     DESIGN.md 4.9); combines with every flag but megakernel.
     roulette: Russian roulette path termination (FLAG_ROULETTE) with the scene's parameters (DeviceScene.set_roulette /
-    MultiScene.set_roulette; 3 and 0.05 by default); combines with every flag but megakernel and stats."""
+    MultiScene.set_roulette; 3 and 0.05 by default); combines with every flag but megakernel and stats.
+    filter: the film through the scene's reconstruction filter instead of the box filter (FLAG_FILTER; DeviceScene.set_filter /
+    MultiScene.set_filter, Mitchell at radius 2 by default): whole-film and tile renders on one rank; not with megakernel or adaptive passes."""
     p = Params()
     _host.hrt_default_params(C.byref(p), width, height, samples)
     p.quirks = quirks
@@ -314,7 +326,7 @@ def default_params(width, height, samples, quirks=QUIRKS_REFERENCE, seed=0, max_
     p.flags = (FLAG_STATS if stats else 0) | (FLAG_MEGAKERNEL if megakernel else 0) | (FLAG_TIMING if timing else 0) | \
               (FLAG_THIN_LENS if thin_lens else 0) | (FLAG_PROGRESS if progress else 0) | (FLAG_NEE if nee or nee_env or nee_emitters or nee_lobes else 0) | \
               (FLAG_NEE_ENV if nee_env else 0) | (FLAG_NEE_EMITTERS if nee_emitters else 0) | (FLAG_NEE_LOBES if nee_lobes else 0) | \
-              (FLAG_STRATIFIED if stratified else 0) | (FLAG_ROULETTE if roulette else 0)
+              (FLAG_STRATIFIED if stratified else 0) | (FLAG_ROULETTE if roulette else 0) | (FLAG_FILTER if filter else 0)
     return p
 
 
@@ -608,6 +620,35 @@ def denoise_resolve_u8(rgb_linear, device=0):
     return out
 
 
+def _filter_kind(kind):
+    if isinstance(kind, str):
+        if kind not in FILTER_KINDS:
+            raise ValueError(f"filter kind must be one of {sorted(FILTER_KINDS)}")
+        return FILTER_KINDS[kind]
+    return int(kind)
+
+
+def filter_samples(rad, kind="mitchell", radius=0.0, width=None, height=None, rect=None, seed=0, stratified=False, device=0):
+    """The reconstruction filter on stored samples (hrt_filter_samples, include/hrt.h), on `device`: rad [S, h, w, 3], the
+    value of each of the S samples of every pixel of `rect` = (x0, y0, w, h) of the width x height film (default: the whole film, w x h)
+    -> the finished film [h, w, 3].  kind: "tent", "bspline", "mitchell" or a FILTER_* value; radius <= 0: the kind's default.  The
+    jitters are those of a render with `seed` and, with stratified, FLAG_STRATIFIED."""
+    rad = _f32(rad)
+    if rad.ndim != 4 or rad.shape[3] != 3:
+        raise ValueError("filter_samples takes rad [samples, h, w, 3]")
+    S, h, w = rad.shape[:3]
+    if rect is None:
+        rect = (0, 0, w, h)
+    if tuple(rect[2:]) != (w, h):
+        raise ValueError("rad must hold rect's h x w pixels")
+    W = w if width is None else width
+    H = h if height is None else height
+    out = np.empty((h, w, 3), np.float32)
+    _check(_hip.hrt_filter_samples(device, _filter_kind(kind), radius, W, H, Rect(*rect), seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF,
+                                   1 if stratified else 0, S, _ptr(rad), _ptr(out)))
+    return out
+
+
 def despeckle_defaults(**params):
     """hrt_despeckle_defaults, then the given fields (radius, rank, ratio, gate_z, repair_invalid) -> DespeckleParams."""
     p = DespeckleParams()
@@ -755,6 +796,18 @@ class DeviceScene:
         first_bounce-th scatter on, no survival probability below q_floor.  HrtError (HRT_ERR_INVALID) for first_bounce < 0 or a q_floor
         outside (0, 1]."""
         _check(_hip.hrt_scene_set_roulette(self._h, first_bounce, q_floor))
+
+    def set_filter(self, kind="mitchell", radius=0.0):
+        """FLAG_FILTER's parameters for the renders of this scene that follow (hrt_scene_set_filter): kind "tent", "bspline", "mitchell"
+        or a FILTER_* value; radius in pixels, <= 0: the kind's default (1, 2, 2).  HrtError (HRT_ERR_INVALID) for an unknown kind, a
+        NaN radius or one outside [0.5, 2.5]."""
+        _check(_hip.hrt_scene_set_filter(self._h, _filter_kind(kind), radius))
+
+    def filter_ms(self):
+        """The time the filter's own kernels took in this scene's render calls since the last call of this, in ms (hrt_scene_filter_ms)."""
+        ms = C.c_double(0.0)
+        _check(_hip.hrt_scene_filter_ms(self._h, C.byref(ms)))
+        return ms.value
 
     def render_tile(self, cam, params, rect=None):
         """-> (h, w, 3) fp32 linear film tile, Stats."""
@@ -996,6 +1049,15 @@ class MultiScene:
     def set_roulette(self, first_bounce=ROULETTE_FIRST_BOUNCE, q_floor=ROULETTE_Q_FLOOR):
         """DeviceScene.set_roulette for every device of the session (hrt_multi_set_roulette)."""
         _check(_hip.hrt_multi_set_roulette(self._h, first_bounce, q_floor))
+
+    def set_filter(self, kind="mitchell", radius=0.0):
+        """DeviceScene.set_filter for every device of the session (hrt_multi_set_filter)."""
+        _check(_hip.hrt_multi_set_filter(self._h, _filter_kind(kind), radius))
+
+    def filter_ms(self):
+        ms = C.c_double(0.0)
+        _check(_hip.hrt_multi_filter_ms(self._h, C.byref(ms)))
+        return ms.value
 
     def progress(self):
         d, t = C.c_uint64(0), C.c_uint64(0)

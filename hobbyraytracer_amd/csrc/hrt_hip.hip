@@ -1457,6 +1457,13 @@ __global__ __launch_bounds__(256, DEPTH <= 24 ? 4 : 3) void k_wf_tail(DScene sc,
 extern "C" __attribute__((visibility("hidden"))) void hrt_wf_merge_launch(float4* s0, float4* s1, float4* s2, float* s3, const unsigned* live, unsigned T,
                                                                           unsigned n_tasks, unsigned K, unsigned* live_m, unsigned* qn_m, unsigned* rn_m,
                                                                           hipStream_t stream);
+// k_flt_gather / k_flt_finish (hrt_filter.hip, a unit of its own): HRT_FLAG_FILTER's film write in place of k_wf_reduce's
+extern "C" __attribute__((visibility("hidden"))) hrt_status hrt_filter_resolve(int32_t kind, float radius, float* resolved);
+extern "C" __attribute__((visibility("hidden"))) hipError_t hrt_filter_gather_launch(int32_t kind, float radius, int32_t W, hrt_rect rect, uint32_t seed_lo, uint32_t seed_hi,
+                                                                                     int strat, const float4* rad, const float4* direct, unsigned n_local, int s0,
+                                                                                     int chunk, int first, int finish, float* acc, hipStream_t stream);
+extern "C" __attribute__((visibility("hidden"))) hipError_t hrt_filter_finish_launch(int32_t kind, float radius, int32_t W, hrt_rect rect, uint32_t seed_lo, uint32_t seed_hi,
+                                                                                     int strat, int samples, float* acc, hipStream_t stream);
 
 // Per pixel: add the batch's samples IN SAMPLE ORDER (main.cpp:118-124); divide once all samples are in (main.cpp:126).
 // NEE: a sample's value is rad + direct (result + the shadow terms), formed before it is added.
@@ -1752,9 +1759,9 @@ struct hrt_scene {
     WfWorkspace wf;
     // events of launches not yet folded into kernel_ms / traversal_ms
     struct Pending { hipEvent_t a, b; };
-    std::vector<Pending> pending, pending_trav;
+    std::vector<Pending> pending, pending_trav, pending_flt;   // (pending_flt: HRT_FLAG_FILTER's launches, hrt_scene_filter_ms)
     std::vector<hipEvent_t> event_pool;
-    double kernel_ms = 0.0, traversal_ms = 0.0;
+    double kernel_ms = 0.0, traversal_ms = 0.0, filter_ms = 0.0;
     uint64_t launches = 0, traversal_launches = 0;
     // HRT_FLAG_PROGRESS: paths ended so far, in host memory mapped into the device (h_ / d_ are the two views of one word),
     // and what the host adds to it: paths of finished batches of the running call, and the call's total
@@ -1778,6 +1785,12 @@ struct hrt_scene {
     // HRT_FLAG_ROULETTE: the rule's two parameters (hrt_scene_set_roulette), kernel arguments of k_wf_shade_rr / k_wf_shade_st_rr
     int32_t rr_first = HRT_ROULETTE_FIRST_BOUNCE;
     float rr_floor = HRT_ROULETTE_Q_FLOOR;
+    // HRT_FLAG_FILTER: the filter's kind and resolved radius (hrt_scene_set_filter), and the film k_wf_reduce writes to when the
+    // gather of hrt_filter.hip writes the real one (flt_cap floats, grown on demand)
+    int32_t flt_kind = HRT_FILTER_MITCHELL;
+    float flt_radius = 2.0f;
+    DevBuf flt_scratch;
+    size_t flt_cap = 0;
 };
 
 namespace {
@@ -1997,6 +2010,7 @@ hrt_status check_params(const hrt_params* p) {
     if ((p->flags & HRT_FLAG_MEGAKERNEL) && (p->flags & HRT_FLAG_NEE)) return fail(HRT_ERR_UNSUPPORTED, "next-event estimation renders on the wavefront pipeline only");
     if ((p->flags & HRT_FLAG_MEGAKERNEL) && (p->flags & HRT_FLAG_STRATIFIED)) return fail(HRT_ERR_UNSUPPORTED, "the stratified sampler renders on the wavefront pipeline only");
     if ((p->flags & HRT_FLAG_MEGAKERNEL) && (p->flags & HRT_FLAG_ROULETTE)) return fail(HRT_ERR_UNSUPPORTED, "Russian roulette renders on the wavefront pipeline only");
+    if ((p->flags & HRT_FLAG_MEGAKERNEL) && (p->flags & HRT_FLAG_FILTER)) return fail(HRT_ERR_UNSUPPORTED, "the reconstruction filter renders on the wavefront pipeline only");
     if ((p->flags & HRT_FLAG_STATS) && (p->flags & HRT_FLAG_ROULETTE)) return fail(HRT_ERR_UNSUPPORTED, "HRT_FLAG_ROULETTE has no counting kernels (HRT_FLAG_STATS); rays and shadow_rays are counted without them");
     return HRT_OK;
 }
@@ -2018,6 +2032,13 @@ hrt_status env_table_device(const float* d_texels, int W, int H, int channels, f
 
 hrt_status check_stripes(int32_t R, int32_t rank, int32_t G) {
     if (R <= 0 || G <= 0 || rank < 0 || rank >= G) return fail(HRT_ERR_INVALID, "bad stripe partition");
+    return HRT_OK;
+}
+
+// HRT_FLAG_FILTER gathers from neighbouring rows: a rank of several does not hold them
+hrt_status check_filter_ranks(const hrt_params* p, int32_t G) {
+    if ((p->flags & HRT_FLAG_FILTER) && G > 1)
+        return fail(HRT_ERR_UNSUPPORTED, "the reconstruction filter needs the whole film on one rank (n_ranks == 1, a session of one device): neighbouring rows belong to other ranks");
     return HRT_OK;
 }
 
@@ -2154,6 +2175,15 @@ hrt_status launch_wavefront(hrt_scene* sc, const hrt_camera* cam, const hrt_para
     // HRT_FLAG_ROULETTE: k_wf_shade_rr / k_wf_shade_st_rr, which end paths of low throughput (hrt_roulette.h); check_params
     // has refused the flag together with HRT_FLAG_STATS, so only their <false, ...> instantiations exist
     const bool rr = (pr->flags & HRT_FLAG_ROULETTE) != 0;
+    // HRT_FLAG_FILTER: the film is written by hrt_filter.hip's gather over the batch's rad / direct; k_wf_reduce still
+    // runs, for the counters it folds, into a film of its own that nobody reads.  (List maps never get here: check_adaptive.)
+    const bool filter = (pr->flags & HRT_FLAG_FILTER) != 0 && map.mode != 2;
+    if (filter && sc->flt_cap < 3 * (size_t)n_local) {
+        HIPCHK(hipDeviceSynchronize());       // an earlier asynchronous render may still write the old one
+        sc->flt_cap = 0;
+        HRTCHK(sc->flt_scratch.alloc(3 * (size_t)n_local * sizeof(float), "hipMalloc(filter: k_wf_reduce's film)"));
+        sc->flt_cap = 3 * (size_t)n_local;
+    }
     size_t cap = wf_max_slots(sc, nee, lobes);
     const int s_end = s_first + s_count;
     int chunk = (int)std::min<size_t>((size_t)s_count, std::max<size_t>(1, cap / n_local));
@@ -2432,7 +2462,21 @@ hrt_status launch_wavefront(hrt_scene* sc, const hrt_camera* cam, const hrt_para
         if (map.mode == 2)
             hipLaunchKernelGGL(nee ? k_wf_reduce_list<true> : k_wf_reduce_list<false>, dim3(rblocks), dim3(256), 0, stream, w.rad, map.pix, n_local, c, s0 == 0 ? 1 : 0, s0 + c, d_out, d_sq, d_count,
                                sc->d_counters, w.wave_rays, w.n_wave_rays, (const float4*)w.direct, w.wave_shadow);
-        else
+        else if (filter) {
+            hipLaunchKernelGGL(nee ? k_wf_reduce<true> : k_wf_reduce<false>, dim3(rblocks), dim3(256), 0, stream, w.rad, n_local, c, 1, 0, pr->samples, sc->flt_scratch.get<float>(),
+                               sc->d_counters, w.wave_rays, w.n_wave_rays, (const float4*)w.direct, w.wave_shadow);
+            const hrt_rect rect{map.mode == 0 ? map.x0 : 0, map.mode == 0 ? map.y0 : 0, map.rw, map.rh};   // (one rank's stripes are the whole film)
+            const bool whole = s0 == 0 && c >= pr->samples;   // one batch holds every sample: the gather sums the weights too and finishes the pixels
+            hipEvent_t fa = nullptr, fb = nullptr;     // the two kernels' own time, for hrt_scene_filter_ms
+            HRTCHK(get_event(sc, &fa)); HRTCHK(get_event(sc, &fb));
+            HIPCHK(hipEventRecord(fa, stream));
+            HIPCHK(hrt_filter_gather_launch(sc->flt_kind, sc->flt_radius, pr->width, rect, pr->seed_lo, pr->seed_hi, strat ? 1 : 0, w.rad, nee ? (const float4*)w.direct : nullptr,
+                                            n_local, s0, c, s0 == 0 ? 1 : 0, whole ? 1 : 0, d_out, stream));
+            if (s0 + c >= pr->samples && !whole)
+                HIPCHK(hrt_filter_finish_launch(sc->flt_kind, sc->flt_radius, pr->width, rect, pr->seed_lo, pr->seed_hi, strat ? 1 : 0, pr->samples, d_out, stream));
+            HIPCHK(hipEventRecord(fb, stream));
+            sc->pending_flt.push_back({fa, fb});
+        } else
             hipLaunchKernelGGL(nee ? k_wf_reduce<true> : k_wf_reduce<false>, dim3(rblocks), dim3(256), 0, stream, w.rad, n_local, c, s0 == 0 ? 1 : 0, s0 + c >= pr->samples ? 1 : 0, pr->samples, d_out,
                                sc->d_counters, w.wave_rays, w.n_wave_rays, (const float4*)w.direct, w.wave_shadow);
         if (progress) {
@@ -2488,6 +2532,7 @@ hrt_status fold_events(hrt_scene* sc, std::vector<hrt_scene::Pending>& list, dou
 }
 hrt_status fold_pending(hrt_scene* sc) {
     HRTCHK(fold_events(sc, sc->pending, sc->kernel_ms, nullptr));
+    HRTCHK(fold_events(sc, sc->pending_flt, sc->filter_ms, nullptr));
     return fold_events(sc, sc->pending_trav, sc->traversal_ms, &sc->traversal_launches);
 }
 
@@ -2589,6 +2634,7 @@ void hrt_scene_destroy(hrt_scene* sc) {
     (void)hipSetDevice(sc->device);
     for (auto& p : sc->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (auto& p : sc->pending_trav) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
+    for (auto& p : sc->pending_flt) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (hipEvent_t e : sc->event_pool) (void)hipEventDestroy(e);
     if (sc->h_progress) (void)hipHostFree((void*)sc->h_progress);
     delete sc;   // (and with it the device buffers)
@@ -2735,6 +2781,26 @@ hrt_status hrt_scene_set_roulette(hrt_scene* sc, int32_t first_bounce, float q_f
     return HRT_OK;
 }
 
+hrt_status hrt_scene_set_filter(hrt_scene* sc, int32_t kind, float radius) {
+    float R = 0.0f;
+    HRTCHK(hrt_filter_resolve(kind, radius, &R));
+    if (!sc) return fail(HRT_ERR_INVALID, "scene is NULL");
+    sc->flt_kind = kind; sc->flt_radius = R;
+    return HRT_OK;
+}
+
+hrt_status hrt_scene_filter_ms(hrt_scene* sc, double* ms) {
+    HRT_API_TRY
+    if (!sc || !ms) return fail(HRT_ERR_INVALID, "NULL argument");
+    HIPCHK(hipSetDevice(sc->device));
+    HIPCHK(hipDeviceSynchronize());
+    HRTCHK(fold_pending(sc));
+    *ms = sc->filter_ms;
+    sc->filter_ms = 0.0;
+    return HRT_OK;
+    HRT_API_CATCH
+}
+
 int32_t hrt_stripe_rows(int32_t height, int32_t R, int32_t rank, int32_t G) {
     if (height <= 0 || R <= 0 || G <= 0 || rank < 0 || rank >= G) return 0;
     const int32_t n_blocks = (height + R - 1) / R;
@@ -2762,6 +2828,7 @@ hrt_status hrt_render_stripes_accumulate_device(hrt_scene* sc, const hrt_camera*
     if (!sc || !cam || !d_accum) return fail(HRT_ERR_INVALID, "NULL argument");
     HRTCHK(check_params(pr));
     HRTCHK(check_stripes(R, rank, G));
+    HRTCHK(check_filter_ranks(pr, G));
     HIPCHK(hipSetDevice(sc->device));
     return launch_pathtrace(sc, cam, pr, stripe_map(pr->width, pr->height, R, rank, G), d_accum, (hipStream_t)stream, sample_first, sample_count);
     HRT_API_CATCH
@@ -2773,6 +2840,7 @@ hrt_status hrt_render_stripes_accumulate(hrt_scene* sc, const hrt_camera* cam, c
     if (!sc || !cam || !accum) return fail(HRT_ERR_INVALID, "NULL argument");
     HRTCHK(check_params(pr));
     HRTCHK(check_stripes(R, rank, G));
+    HRTCHK(check_filter_ranks(pr, G));
     const size_t bytes = (size_t)hrt_stripe_rows(pr->height, R, rank, G) * pr->width * 3 * sizeof(float);
     return render_via_host(sc, stats, {{accum, bytes}}, sample_first > 0, "accumulation buffer", [&](void* const* d, bool&) {
         return hrt_render_stripes_accumulate_device(sc, cam, pr, R, rank, G, (float*)d[0], sample_first, sample_count, nullptr);
@@ -2787,6 +2855,7 @@ hrt_status check_adaptive(hrt_scene* sc, const hrt_camera* cam, const hrt_params
     HRTCHK(check_params(pr));
     HRTCHK(check_stripes(R, rank, G));
     if (pr->flags & HRT_FLAG_MEGAKERNEL) return fail(HRT_ERR_UNSUPPORTED, "adaptive sampling renders on the wavefront pipeline only");
+    if (pr->flags & HRT_FLAG_FILTER) return fail(HRT_ERR_UNSUPPORTED, "adaptive passes render lists of pixels, which have no neighbours: no reconstruction filter (HRT_FLAG_FILTER)");
     if (ad->min_samples < 2 || ad->min_samples > pr->samples) return fail(HRT_ERR_INVALID, "min_samples must lie in [2, samples]");
     if (ad->pass_samples < 1) return fail(HRT_ERR_INVALID, "pass_samples must be >= 1");
     if (!(ad->threshold >= 0.0f) || !(ad->floor >= 0.0f)) return fail(HRT_ERR_INVALID, "threshold and floor must be >= 0 (and not NaN)");
@@ -2932,6 +3001,7 @@ hrt_status hrt_render_stripes(hrt_scene* sc, const hrt_camera* cam, const hrt_pa
     if (!sc || !cam || !out) return fail(HRT_ERR_INVALID, "NULL argument");
     HRTCHK(check_params(pr));
     HRTCHK(check_stripes(R, rank, G));
+    HRTCHK(check_filter_ranks(pr, G));
     const size_t bytes = (size_t)hrt_stripe_rows(pr->height, R, rank, G) * pr->width * 3 * sizeof(float);
     return render_via_host(sc, stats, {{out, bytes}}, false, "film stripes", [&](void* const* d, bool&) {
         return hrt_render_stripes_device(sc, cam, pr, R, rank, G, (float*)d[0], nullptr);
@@ -3373,6 +3443,25 @@ hrt_status hrt_multi_set_roulette(hrt_multi* m, int32_t first_bounce, float q_fl
     return HRT_OK;
 }
 
+hrt_status hrt_multi_set_filter(hrt_multi* m, int32_t kind, float radius) {
+    float R = 0.0f;
+    HRTCHK(hrt_filter_resolve(kind, radius, &R));
+    if (!m) return fail(HRT_ERR_INVALID, "session is NULL");
+    for (hrt_scene* s : m->scenes) { s->flt_kind = kind; s->flt_radius = R; }
+    return HRT_OK;
+}
+
+hrt_status hrt_multi_filter_ms(hrt_multi* m, double* ms) {
+    if (!m || !ms) return fail(HRT_ERR_INVALID, "NULL argument");
+    *ms = 0.0;
+    for (hrt_scene* s : m->scenes) {      // (a filtered session has one device)
+        double one = 0.0;
+        HRTCHK(hrt_scene_filter_ms(s, &one));
+        *ms = std::max(*ms, one);
+    }
+    return HRT_OK;
+}
+
 int32_t hrt_multi_devices(const hrt_multi* m) { return m ? (int32_t)m->devices.size() : 0; }
 int32_t hrt_multi_uses_rccl(const hrt_multi* m) { return m && m->use_rccl ? 1 : 0; }
 
@@ -3382,6 +3471,7 @@ hrt_status hrt_multi_render(hrt_multi* m, const hrt_camera* cam, const hrt_param
     if (!m || !cam) return fail(HRT_ERR_INVALID, "NULL argument");
     HRTCHK(check_params(pr));
     if (R <= 0) return fail(HRT_ERR_INVALID, "rows_per_block must be positive");
+    HRTCHK(check_filter_ranks(pr, (int32_t)m->devices.size()));
     if (sample_count < 0) sample_count = pr->samples - sample_first;
     if (sample_first < 0 || sample_count < 0 || sample_first + sample_count > pr->samples) return fail(HRT_ERR_INVALID, "sample range outside [0, samples)");
     const int G = (int)m->devices.size();

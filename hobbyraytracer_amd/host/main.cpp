@@ -61,6 +61,12 @@
 //     --despeckle-gate Z (finite, >= 0; 2; 0 switches the gate off)   (each implies --despeckle)
 //     --despeckle-map FILE.pfm (needs --despeckle: 1 - s where a pixel was brought down to a share s of itself, -1 where a non-finite
 //         pixel was repaired, 0 elsewhere; in all three channels)
+//     --filter tent|bspline|mitchell (the film's reconstruction filter, DESIGN.md 4.16: a pixel is the weighted mean of the samples of
+//         its neighbourhood instead of the mean of its own, the box filter; the same paths, the same rays.  One GPU; not with --adaptive,
+//         --checkpoint / --resume, --denoise-variance measured or --denoise-batches.  Combines with the --nee flags, --stratified, --roulette,
+//         --lens, --progressive, --aov*, --despeckle and --denoise; the previews of --progressive show the unnormalised sums over the
+//         samples done, and the feature buffers of --aov stay box-filtered)
+//     --filter-radius X (the filter's radius in pixels, 0.5 .. 2.5; tent 1, bspline 2, mitchell 2 by default; needs --filter)
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -98,6 +104,9 @@ int main(int argc, char** argv) {
     auto start = std::chrono::high_resolution_clock::now();
     std::string file = "teapot_scene.yaml";  // main.cpp:146
     std::string assets, out, makeAssets, dumpLinear, dumpNoisy, sampleMap, aovPrefix, dumpVariance, despeckleMap;
+    std::string filterName;
+    bool haveFilterRadius = false;
+    double filter_s = 0.0;
     bool despeckle = false;
     hrt_despeckle_params dsp;
     hrt_despeckle_defaults(&dsp);
@@ -231,6 +240,16 @@ int main(int argc, char** argv) {
             denoise = true;
             if (!haveVarianceMode) measured = true;
         }
+        else if (a == "--filter") {
+            filterName = next("--filter");
+            opt.filter_kind = filterName == "tent" ? HRT_FILTER_TENT : filterName == "bspline" ? HRT_FILTER_BSPLINE : filterName == "mitchell" ? HRT_FILTER_MITCHELL : -1;
+            if (opt.filter_kind < 0) { std::cerr << "--filter takes tent, bspline or mitchell" << std::endl; return 2; }
+        }
+        else if (a == "--filter-radius") {
+            opt.filter_radius = number("--filter-radius", next("--filter-radius"));
+            if (!(opt.filter_radius >= 0.5f && opt.filter_radius <= 2.5f)) { std::cerr << "--filter-radius takes a number from 0.5 to 2.5" << std::endl; return 2; }
+            haveFilterRadius = true;
+        }
         else if (a == "--despeckle") despeckle = true;
         else if (a == "--despeckle-rank" || a == "--despeckle-radius") {
             const bool isRank = a == "--despeckle-rank";
@@ -261,6 +280,13 @@ int main(int argc, char** argv) {
         if (opt.min_samples < 2) { std::cerr << "--min-samples must be >= 2" << std::endl; return 2; }
         if (opt.pass_samples <= 0) opt.pass_samples = 16;
     } else if (!sampleMap.empty()) { std::cerr << "--sample-map needs --adaptive" << std::endl; return 2; }
+    if (haveFilterRadius && opt.filter_kind < 0) { std::cerr << "--filter-radius needs --filter tent|bspline|mitchell" << std::endl; return 2; }
+    if (opt.filter_kind >= 0) {
+        const char* why = opt.adaptive >= 0.0f ? "--adaptive" : opt.gpus > 1 ? "--gpus N > 1" : !opt.checkpoint.empty() ? "--checkpoint" : opt.resume ? "--resume" :
+                          measured ? "--denoise-variance measured / --denoise-batches" : nullptr;
+        if (why) { std::cerr << "--filter cannot be combined with " << why << std::endl; return 2; }
+        opt.filter_seconds = &filter_s;
+    }
     if (haveAovSpp && aovPrefix.empty() && !denoise) { std::cerr << "--aov-spp needs --aov PREFIX" << std::endl; return 2; }
     if (aovIds && aovPrefix.empty()) { std::cerr << (mattes.empty() ? "--aov-ids" : "--matte") << " needs --aov PREFIX" << std::endl; return 2; }
     if (!dumpNoisy.empty() && !denoise && !despeckle) { std::cerr << "--dump-noisy needs --denoise or --despeckle" << std::endl; return 2; }
@@ -456,6 +482,10 @@ int main(int argc, char** argv) {
         if (despeckle) {              // the outlier filter (and, without --denoise, the resolve): the wall time, copies included; the counts from its map
             const size_t k = std::strlen(extra);
             std::snprintf(extra + k, sizeof(extra) - k, ", \"despeckle_s\": %.6f, \"despeckle_pixels\": %llu, \"despeckle_repaired\": %llu", despeckle_s, despecklePixels, despeckleRepaired);
+        }
+        if (opt.filter_kind >= 0) {   // the reconstruction filter: its kind and the time of its own kernels, from HIP events
+            const size_t k = std::strlen(extra);
+            std::snprintf(extra + k, sizeof(extra) - k, ", \"filter\": \"%s\", \"filter_s\": %.6f", filterName.c_str(), filter_s);
         }
         if (measured) {               // the measured variance: the wall time of its folds on the first device, copies included
             const size_t k = std::strlen(extra);

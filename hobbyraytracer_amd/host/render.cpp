@@ -265,7 +265,7 @@ hrt_status render(int /*nThreads*/, const std::shared_ptr<Texture> background, c
     pr.flags = (opt.stats && !opt.roulette ? HRT_FLAG_STATS : 0) | (opt.thin_lens ? HRT_FLAG_THIN_LENS : 0) | (opt.progress ? HRT_FLAG_PROGRESS : 0) |
                (opt.nee ? HRT_FLAG_NEE : 0) | (opt.nee && opt.nee_env ? HRT_FLAG_NEE_ENV : 0) |
                (opt.nee && opt.nee_emitters ? HRT_FLAG_NEE_EMITTERS : 0) | (opt.nee && opt.nee_lobes ? HRT_FLAG_NEE_LOBES : 0) |
-               (opt.stratified ? HRT_FLAG_STRATIFIED : 0) | (opt.roulette ? HRT_FLAG_ROULETTE : 0);
+               (opt.stratified ? HRT_FLAG_STRATIFIED : 0) | (opt.roulette ? HRT_FLAG_ROULETTE : 0) | (opt.filter_kind >= 0 ? HRT_FLAG_FILTER : 0);
 
     if (opt.aov_samples > 0 && opt.aov_out && opt.aov_ids_out) {
         if (fb.prims.size() >= (1u << 24) || fb.materials.size() >= (1u << 24)) {
@@ -287,6 +287,11 @@ hrt_status render(int /*nThreads*/, const std::shared_ptr<Texture> background, c
     }
     if (opt.roulette && (st = hrt_multi_set_roulette(multi, opt.roulette_start, opt.roulette_floor)) != HRT_OK) {
         std::cerr << "hrt_multi_set_roulette: " << hrt_status_str(st) << ": " << hrt_last_error() << std::endl;
+        hrt_multi_destroy(multi);
+        return st;
+    }
+    if (opt.filter_kind >= 0 && (st = hrt_multi_set_filter(multi, opt.filter_kind, opt.filter_radius)) != HRT_OK) {
+        std::cerr << "hrt_multi_set_filter: " << hrt_status_str(st) << ": " << hrt_last_error() << std::endl;
         hrt_multi_destroy(multi);
         return st;
     }
@@ -418,6 +423,10 @@ hrt_status render(int /*nThreads*/, const std::shared_ptr<Texture> background, c
         if (st != HRT_OK) std::cerr << "\nvariance: " << hrt_status_str(st) << ": " << hrt_last_error() << std::endl;
     }
     if (opt.variance_seconds) *opt.variance_seconds = vseconds;
+    if (opt.filter_seconds) {
+        double ms = 0.0;
+        if (hrt_multi_filter_ms(multi, &ms) == HRT_OK) *opt.filter_seconds = ms * 1e-3;
+    }
     stopReporter();
     std::cout << "\rPixels rendered: " << numPixels << "/" << numPixels << std::flush << "\n";
     hrt_multi_destroy(multi);

@@ -24,6 +24,9 @@ struct RenderOptions {
     bool roulette = false;              // Russian roulette (--roulette, HRT_FLAG_ROULETTE) ...
     int roulette_start = 3;             // ... from a path's N-th scatter on (--roulette-start N)
     float roulette_floor = 0.05f;       // ... with no survival probability below Q (--roulette-floor Q)
+    int filter_kind = -1;               // the film's reconstruction filter (--filter, HRT_FLAG_FILTER): HRT_FILTER_*, -1 = the box filter ...
+    float filter_radius = 0.0f;         // ... at this radius in pixels (--filter-radius; <= 0: the kind's default).  One device, no adaptive passes
+    double* filter_seconds = nullptr;   // ... (optional) gets the time of the filter's own kernels, from HIP events
     bool force_rccl = false;            // gather through an RCCL communicator even with one device (--rccl; tests)
     uint32_t quirks = HRT_QUIRKS_REFERENCE;
     uint64_t seed = 0;

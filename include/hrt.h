@@ -272,7 +272,7 @@ enum {
                                     batch size and adaptive schedule, as without the flag.  Combines with every flag but
                                     HRT_FLAG_MEGAKERNEL (HRT_ERR_UNSUPPORTED).  The estimate stays unbiased; the samples of a pixel are no
                                     longer independent, so hrt_render_adaptive's variance estimate over-states the error of the mean. */
-    HRT_FLAG_ROULETTE = 1u << 10 /* Russian roulette (off = every path is followed until it escapes, is absorbed or reaches
+    HRT_FLAG_ROULETTE = 1u << 10,/* Russian roulette (off = every path is followed until it escapes, is absorbed or reaches
                                     max_depth): at every vertex that scatters, from the first_bounce-th scatter of a path on, the path
                                     survives with probability q = max(q_floor, min(1, the largest component of its attenuation)) and a
                                     survivor's attenuation is divided by q (csrc/hrt_roulette.h; the parameters: hrt_scene_set_roulette,
@@ -281,6 +281,15 @@ enum {
                                     unbiased; hrt_stats::rays and shadow_rays count what was traced, which is less than without the flag.
                                     Combines with the NEE flags and HRT_FLAG_STRATIFIED; with HRT_FLAG_MEGAKERNEL, and with HRT_FLAG_STATS
                                     (there are no counting variants of its kernels), every render call returns HRT_ERR_UNSUPPORTED. */
+    HRT_FLAG_FILTER = 1u << 11   /* the film reconstruction filter of the scene ("reconstruction filter" below; the kind and
+                                    the radius: hrt_scene_set_filter, Mitchell at radius 2 by default; off = the reference's box filter, a
+                                    pixel is the mean of its own samples): a pixel is the weighted mean of the samples of its neighbourhood.
+                                    The paths, hrt_stats and the workspace are those of the render without the flag.  Honoured by
+                                    hrt_render_tile, by hrt_render_stripes* and the accumulate forms with n_ranks == 1 and by
+                                    hrt_multi_render on a session of one device; HRT_ERR_UNSUPPORTED, output untouched, with n_ranks > 1 or a
+                                    session of more devices (neighbouring rows belong to other ranks), from the adaptive entry points (a
+                                    list of pixels has no neighbours) and with HRT_FLAG_MEGAKERNEL.  The feature buffers and id mattes
+                                    accept the flag and stay box-filtered. */
 };
 
 typedef struct hrt_rect { int32_t x0, y0, w, h; } hrt_rect;   /* y0 = row index from the TOP (pIdx / W) */
@@ -341,6 +350,13 @@ void hrt_scene_destroy(hrt_scene* scene);
  * (0 and 1: from the first) and no path survives with a probability below q_floor.  A new scene has 3 and 0.05.  HRT_ERR_INVALID for
  * first_bounce < 0 and for a q_floor outside (0, 1] or NaN; the scene then keeps what it had.  Without the flag they are not read. */
 hrt_status hrt_scene_set_roulette(hrt_scene* scene, int32_t first_bounce, float q_floor);
+/* HRT_FLAG_FILTER's parameters for the renders of `scene` that follow ("reconstruction filter" below): kind = HRT_FILTER_*, radius in
+ * pixels, radius <= 0 = the kind's default (tent 1, bspline 2, mitchell 2).  A new scene has HRT_FILTER_MITCHELL at 2.  HRT_ERR_INVALID for
+ * an unknown kind, a NaN radius and a radius outside [0.5, 2.5]; the scene then keeps what it had.  Without the flag they are not read. */
+hrt_status hrt_scene_set_filter(hrt_scene* scene, int32_t kind, float radius);
+/* Reads and clears the time the filter's own kernels took in the render calls on `scene` so far, in ms, from HIP events around their
+ * launches (it is part of hrt_stats::kernel_ms too); synchronises the device.  0 when no call had HRT_FLAG_FILTER. */
+hrt_status hrt_scene_filter_ms(hrt_scene* scene, double* ms);
 
 /* Blocking: renders tile (x0,y0,w,h) of the W x H film and writes
  * w*h*3 fp32 LINEAR radiance means (row-major within the tile, row 0 = top)
@@ -667,6 +683,67 @@ hrt_status hrt_despeckle_device(int device, int32_t W, int32_t H, const hrt_desp
 hrt_status hrt_despeckle(int device, int32_t W, int32_t H, const hrt_despeckle_params* params, const float* rgb, const float* var,
                          float* out, float* map);
 
+/* ---- reconstruction filter --------------------------------
+ * HRT_FLAG_FILTER: a pixel of the film is the weighted mean of the samples of its neighbourhood, each weighted by a separable
+ * piecewise-polynomial kernel at the sample's distance from the pixel's centre, instead of the plain mean of its own samples (the box
+ * filter of main.cpp:118-126).  It is a gather over what a render holds anyway -- every sample's radiance and its jitter, which is a pure
+ * function of (seed, pixel, sample) -- so the paths, their weights and hrt_stats are those of the render without the flag.  Everything
+ * is fp32 and uses only + - * /, fabsf and comparisons, evaluated in the order written here without fused multiply-adds, so that a
+ * restatement of these words with IEEE fp32 operations gives the same bits (tests/filter_np.py).  Only whether a value is a NaN is
+ * defined, not a NaN's sign and payload.
+ *
+ * Inputs: the call's rectangle of the W x H film -- a tile, or the whole film as the stripes of one rank; both are row-major, local
+ * pixel lp = ly * rw + lx --, a filter `kind` and a radius R in pixels.
+ *
+ * Per tap.  For the output pixel p = (px, py), sample s and a neighbour pixel q = (qx, qy) inside the rectangle (p itself is one):
+ *   jx = (float)(word x >> 8) * 2^-24, jy likewise from word y, of sample s of pixel q's jitter draw: the RNG_JITTER site at bounce 0
+ *        under (seed, pixel = qy * W + qx, sample = s), Philox or, with HRT_FLAG_STRATIFIED, the stratified sampler (csrc/hrt_rng.h
+ *        rng_draw / strat_draw, u01): what the sample's camera ray adds to x = qx and to y = H - qy
+ *   dx = ((float)(qx - px) + jx) - 0.5f
+ *   dy = ((float)(py - qy) + jy) - 0.5f                    (rows count downwards, the camera's y upwards)
+ *   tx = fabsf(dx) / R,  ty = fabsf(dy) / R
+ *   the tap counts if and only if tx < 1 && ty < 1; a tap that does not count is not added at all (0 * NaN must not poison a pixel)
+ *   w = k(tx) * k(ty)
+ * The kernels k, for t in [0, 1); the two cubics take x = t + t and end in one division:
+ *   HRT_FILTER_TENT      k = 1.0f - t
+ *   HRT_FILTER_BSPLINE   x < 1:      a = 3.0f * x - 6.0f;  a = a * x;  a = a * x;  a = a + 4.0f;  k = a / 6.0f
+ *                        otherwise:  u = 2.0f - x;  a = (u * u) * u;  k = a / 6.0f
+ *   HRT_FILTER_MITCHELL  x < 1:      a = 7.0f * x - 12.0f;  a = a * x;  a = a * x;  a = a + 5.3333335f;  k = a / 6.0f
+ *   (Mitchell-Netravali, otherwise:  a = -2.3333333f * x + 12.0f;  a = a * x - 20.0f;  a = a * x + 10.666667f;  k = a / 6.0f
+ *    B = C = 1/3)                    (the floats nearest 16/3, -7/3 and 32/3; the outer lobe is negative)
+ *
+ * Accumulation, per pixel p:  acc_k = acc_k + w * v_k for each channel k, and Wsum = Wsum + w, over the samples in ascending order and,
+ * within a sample, over the counting taps with qy ascending, then qx ascending.  v is the sample's value, rad or rad + direct per channel
+ * under HRT_FLAG_NEE.  acc starts from +0, or from what the accumulation buffer holds when sample_first > 0.  Which window of neighbours
+ * is visited is not part of the definition: any window that holds every counting tap gives the same bits (half-width 0 for R = 0.5,
+ * 1 for R <= 1.5, 2 for R <= 2.5).
+ *
+ * Finishing.  The call whose sample range reaches params->samples finishes each pixel: Wsum over ALL samples [0, samples) in the order
+ * above, from +0; out_k = Wsum > 0 ? acc_k / Wsum : 0; then out_k = out_k < 0 ? 0 : out_k (Mitchell's negative lobes can leave a
+ * negative sum; a NaN stays a NaN, as in the unfiltered film).  Wsum depends on the jitters only, so the accumulation buffer plus the
+ * next sample index remains the whole state of a render, and any split of [0, samples) into consecutive calls gives the bits of the
+ * one-shot call.  Before the last call the buffer holds the unnormalised acc.
+ *
+ * Edges.  Pixels outside the rectangle contribute nothing, at the film's edges and at a tile's: a sub-tile therefore differs from the
+ * same pixels of the full film along its border, by definition.
+ *
+ * Not part of it: filtering across ranks or devices, filtered feature buffers and adaptive passes, Gaussian and
+ * Lanczos kernels (expf and sinf are not among the operations pinned here). */
+enum {
+    HRT_FILTER_TENT = 0,      /* default radius 1 */
+    HRT_FILTER_BSPLINE = 1,   /* default radius 2 */
+    HRT_FILTER_MITCHELL = 2   /* default radius 2 */
+};
+/* The filter without a scene, on stored samples: rad = [samples][rect.h][rect.w][3] floats, the value of sample s of every pixel of
+ * `rect` of the W x H film (what the film's path under (seed, pixel, s) returned); out = [rect.h][rect.w][3], the finished pixels.  The
+ * jitters are those of a render with this seed and, with stratified = 1, HRT_FLAG_STRATIFIED.  radius <= 0 = the kind's default.
+ * Blocking, HOST buffers, on `device`; the same kernels as a render under HRT_FLAG_FILTER.  HRT_ERR_INVALID, with a message, for an
+ * unknown kind, a NaN radius or one outside [0.5, 2.5], a NULL buffer, W or H below 1 or more than 2^30 pixels, a rectangle that is
+ * empty or not inside the film, samples < 1 and stratified other than 0 or 1 -- decided before any device is touched, and the output is
+ * left untouched. */
+hrt_status hrt_filter_samples(int device, int32_t kind, float radius, int32_t W, int32_t H, hrt_rect rect, uint32_t seed_lo, uint32_t seed_hi,
+                              int32_t stratified, int32_t samples, const float* rad, float* out);
+
 /* ---- multi-GPU session -----------------------------------
  * The reference's render() (main.cpp:81-140) has one parallel loop over all pixels of the film (main.cpp:111-135, no state
  * shared between pixels).  Here the flattened scene is replicated on `n_devices` GPUs of THIS process (`devices` = their
@@ -687,6 +764,10 @@ int32_t hrt_multi_devices(const hrt_multi* m);
 int32_t hrt_multi_uses_rccl(const hrt_multi* m);
 /* hrt_scene_set_roulette for every device of the session. */
 hrt_status hrt_multi_set_roulette(hrt_multi* m, int32_t first_bounce, float q_floor);
+/* hrt_scene_set_filter for every device of the session. */
+hrt_status hrt_multi_set_filter(hrt_multi* m, int32_t kind, float radius);
+/* hrt_scene_filter_ms of the session (the slowest device's). */
+hrt_status hrt_multi_filter_ms(hrt_multi* m, double* ms);
 /* Adds samples [sample_first, sample_first + sample_count) of params->samples on all devices at once (sample_count < 0: all that
  * are left; 0: none, only gather what is there), gathers, and hands out (both optional, caller-owned HOST buffers):
  *   out_sums  W*H*3 floats in film order: the running sums -- the means once the range has reached params->samples
