@@ -18,7 +18,7 @@ HOST_HDR := $(wildcard $(PKG)/host/*.h) $(wildcard $(PKG)/csrc/*.h) $(wildcard i
 
 all: $(PKG)/lib/libhrt_hip.so $(PKG)/lib/libhrt_host.so $(PKG)/bin/hobbyraytracer oracle/liboracle.so
 
-$(PKG)/lib/libhrt_hip.so: $(PKG)/csrc/hrt_hip.hip $(PKG)/csrc/hrt_lbvh.hip $(PKG)/csrc/hrt_sahbvh.hip $(PKG)/csrc/hrt_denoise.hip $(PKG)/csrc/hrt_variance.hip $(PKG)/csrc/hrt_aov_ids.hip $(PKG)/csrc/hrt_merge.hip $(PKG)/csrc/hrt_despeckle.hip $(PKG)/csrc/hrt_filter.hip $(HOST_HDR)
+$(PKG)/lib/libhrt_hip.so: $(PKG)/csrc/hrt_hip.hip $(PKG)/csrc/hrt_lbvh.hip $(PKG)/csrc/hrt_sahbvh.hip $(PKG)/csrc/hrt_denoise.hip $(PKG)/csrc/hrt_variance.hip $(PKG)/csrc/hrt_aov_ids.hip $(PKG)/csrc/hrt_merge.hip $(PKG)/csrc/hrt_despeckle.hip $(PKG)/csrc/hrt_filter.hip $(PKG)/csrc/hrt_develop.hip $(HOST_HDR)
 	@mkdir -p $(PKG)/lib build
 	$(HIPCC) $(HIPFLAGS) -c -o build/hrt_hip.o $(PKG)/csrc/hrt_hip.hip
 	$(HIPCC) $(HIPFLAGS) -c -o build/hrt_lbvh.o $(PKG)/csrc/hrt_lbvh.hip
@@ -29,7 +29,8 @@ $(PKG)/lib/libhrt_hip.so: $(PKG)/csrc/hrt_hip.hip $(PKG)/csrc/hrt_lbvh.hip $(PKG
 	$(HIPCC) $(HIPFLAGS) -c -o build/hrt_merge.o $(PKG)/csrc/hrt_merge.hip
 	$(HIPCC) $(HIPFLAGS) -c -o build/hrt_despeckle.o $(PKG)/csrc/hrt_despeckle.hip
 	$(HIPCC) $(HIPFLAGS) -c -o build/hrt_filter.o $(PKG)/csrc/hrt_filter.hip
-	$(HIPCC) $(HIPFLAGS) -shared -o $@ build/hrt_hip.o build/hrt_lbvh.o build/hrt_sahbvh.o build/hrt_denoise.o build/hrt_variance.o build/hrt_aov_ids.o build/hrt_merge.o build/hrt_despeckle.o build/hrt_filter.o -ldl
+	$(HIPCC) $(HIPFLAGS) -c -o build/hrt_develop.o $(PKG)/csrc/hrt_develop.hip
+	$(HIPCC) $(HIPFLAGS) -shared -o $@ build/hrt_hip.o build/hrt_lbvh.o build/hrt_sahbvh.o build/hrt_denoise.o build/hrt_variance.o build/hrt_aov_ids.o build/hrt_merge.o build/hrt_despeckle.o build/hrt_filter.o build/hrt_develop.o -ldl
 
 $(PKG)/lib/libhrt_host.so: $(HOST_SRC) $(HOST_HDR)
 	@mkdir -p $(PKG)/lib

@@ -139,6 +139,22 @@ class DespeckleParams(C.Structure):
     _fields_ = [("radius", C.c_int32), ("rank", C.c_int32), ("ratio", C.c_float), ("gate_z", C.c_float), ("repair_invalid", C.c_int32)]
 
 
+class DevelopParams(C.Structure):
+    """hrt_develop_params: the develop stage's settings (include/hrt.h); develop_defaults() fills them in."""
+    _fields_ = [("bloom_levels", C.c_int32), ("bloom_strength", C.c_float), ("exposure_mode", C.c_int32), ("exposure_ev", C.c_float),
+                ("key", C.c_float), ("meter_low", C.c_float), ("meter_high", C.c_float), ("meter_floor", C.c_float), ("ev_min", C.c_float),
+                ("ev_max", C.c_float)]
+
+
+class DevelopInfo(C.Structure):
+    """hrt_develop_info: what a develop call measured and applied (include/hrt.h)."""
+    _fields_ = [("mean_ev", C.c_double), ("scale", C.c_float), ("metered", C.c_uint32), ("levels", C.c_uint32), ("pad", C.c_uint32)]
+
+
+DEVELOP_BINS = 2048
+EXPOSURE_NONE, EXPOSURE_MANUAL, EXPOSURE_AUTO = 0, 1, 2
+
+
 class Hit(C.Structure):
     _fields_ = [("t", C.c_float), ("prim", C.c_int32), ("tri", C.c_int32), ("front_face", C.c_int32), ("p", C.c_float * 3),
                 ("normal", C.c_float * 3), ("u", C.c_float), ("v", C.c_float)]
@@ -161,7 +177,8 @@ HIP_SYMBOLS = ["hrt_device_count", "hrt_scene_create", "hrt_scene_destroy", "hrt
                "hrt_variance_state_bytes", "hrt_variance_fold_device", "hrt_variance_finish_device", "hrt_adaptive_variance_device",
                "hrt_variance_fold", "hrt_variance_finish", "hrt_adaptive_variance",
                "hrt_despeckle_defaults", "hrt_despeckle_workspace_bytes", "hrt_despeckle_device", "hrt_despeckle",
-               "hrt_scene_set_filter", "hrt_multi_set_filter", "hrt_filter_samples", "hrt_scene_filter_ms", "hrt_multi_filter_ms"]
+               "hrt_scene_set_filter", "hrt_multi_set_filter", "hrt_filter_samples", "hrt_scene_filter_ms", "hrt_multi_filter_ms",
+               "hrt_develop_defaults", "hrt_develop_workspace_bytes", "hrt_develop_device", "hrt_develop"]
 HOST_SYMBOLS = ["hrt_host_load_yaml", "hrt_host_free", "hrt_host_flat", "hrt_host_film", "hrt_host_camera", "hrt_host_bvh_depth",
                 "hrt_default_params", "hrt_asset_write_teapot_obj", "hrt_asset_write_bust_obj", "hrt_asset_write_hall_hdr",
                 "hrt_host_write_image", "hrt_host_read_hdr", "hrt_host_read_png", "hrt_host_read_jpeg", "hrt_host_write_hdr", "hrt_host_write_pfm", "hrt_host_read_pfm", "hrt_host_last_error", "hrt_host_set_bvh_builder"]
@@ -253,6 +270,12 @@ _hip.hrt_multi_set_filter.argtypes = [_vp, C.c_int32, C.c_float]
 _hip.hrt_scene_filter_ms.argtypes = [_vp, C.POINTER(C.c_double)]
 _hip.hrt_multi_filter_ms.argtypes = [_vp, C.POINTER(C.c_double)]
 _hip.hrt_filter_samples.argtypes = [C.c_int, C.c_int32, C.c_float, C.c_int32, C.c_int32, Rect, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, _fp, _fp]
+_hip.hrt_develop_defaults.argtypes = [C.POINTER(DevelopParams)]
+_hip.hrt_develop_defaults.restype = None
+_hip.hrt_develop_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+_hip.hrt_develop_workspace_bytes.restype = C.c_uint64
+_hip.hrt_develop_device.argtypes = [C.c_int, C.c_int32, C.c_int32, C.POINTER(DevelopParams), _vp, _vp, _vp, _vp, _vp, _vp]
+_hip.hrt_develop.argtypes = [C.c_int, C.c_int32, C.c_int32, C.POINTER(DevelopParams), _fp, _fp, C.POINTER(DevelopInfo), C.POINTER(C.c_uint32)]
 _hip.hrt_math_probe.argtypes = [C.c_int, C.c_int32, C.c_int64, _fp, _fp, _fp]
 _hip.hrt_sampler_probe.argtypes = [C.c_int, C.c_uint64, C.c_int64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
 _hip.hrt_env_table_build.argtypes = [_fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp]
@@ -693,6 +716,51 @@ def despeckle_device(width, height, d_rgb_ptr, d_out_ptr, d_workspace_ptr, d_var
     p = params if params is not None else despeckle_defaults()
     _check(_hip.hrt_despeckle_device(device, width, height, C.byref(p), _vp(d_rgb_ptr), _vp(d_var_ptr) if d_var_ptr else None, _vp(d_out_ptr),
                                      _vp(d_map_ptr) if d_map_ptr else None, _vp(d_workspace_ptr), _vp(stream)))
+
+
+def develop_defaults(**params):
+    """hrt_develop_defaults, then the given fields (bloom_levels, bloom_strength, exposure_mode, exposure_ev, key, meter_low, meter_high,
+    meter_floor, ev_min, ev_max) -> DevelopParams.  The defaults are the identity."""
+    p = DevelopParams()
+    _hip.hrt_develop_defaults(C.byref(p))
+    names = [n for n, _ in DevelopParams._fields_]
+    for k, v in params.items():
+        if k not in names:
+            raise TypeError(f"hrt_develop_params has no field {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def develop_workspace_bytes(width, height, levels):
+    return int(_hip.hrt_develop_workspace_bytes(width, height, levels))
+
+
+def develop(rgb, device=0, return_info=False, return_histogram=False, **params):
+    """The develop stage (hrt_develop, include/hrt.h) on `device`: the linear film rgb [H, W, 3] -> the developed film
+    [H, W, 3], after a pyramid bloom (bloom_levels, bloom_strength) and an exposure (exposure_mode = EXPOSURE_NONE, EXPOSURE_MANUAL with
+    exposure_ev, or EXPOSURE_AUTO, metered from the film).  With return_info also a DevelopInfo (mean_ev, scale, metered, levels), with
+    return_histogram also the 2048 bin counts of the meter as uint32.  **params: fields of DevelopParams that differ from the defaults."""
+    rgb = _f32(rgb)
+    if rgb.ndim != 3 or rgb.shape[2] != 3:
+        raise ValueError("develop takes rgb [H, W, 3]")
+    H, W = rgb.shape[:2]
+    p = develop_defaults(**params)
+    out = np.empty_like(rgb)
+    info = DevelopInfo() if return_info else None
+    hist = np.zeros(DEVELOP_BINS, np.uint32) if return_histogram else None
+    _check(_hip.hrt_develop(device, W, H, C.byref(p), _ptr(rgb), _ptr(out), C.byref(info) if info is not None else None,
+                            hist.ctypes.data_as(C.POINTER(C.c_uint32)) if hist is not None else None))
+    res = (out,) + ((info,) if return_info else ()) + ((hist,) if return_histogram else ())
+    return res if len(res) > 1 else out
+
+
+def develop_device(width, height, d_rgb_ptr, d_out_ptr, d_workspace_ptr, d_info_ptr=None, d_hist_ptr=None, device=0, stream=0, params=None):
+    """Asynchronous (hrt_develop_device): raw device pointers (e.g. torch tensors' .data_ptr()) to rgb [H, W, 3], out [H, W, 3] (which may
+    be rgb itself), a workspace of develop_workspace_bytes(width, height, params.bloom_levels) and, optionally, room for one DevelopInfo
+    (24 bytes, 8-byte aligned) and for the 2048 uint32 bin counts."""
+    p = params if params is not None else develop_defaults()
+    _check(_hip.hrt_develop_device(device, width, height, C.byref(p), _vp(d_rgb_ptr), _vp(d_out_ptr), _vp(d_info_ptr) if d_info_ptr else None,
+                                   _vp(d_hist_ptr) if d_hist_ptr else None, _vp(d_workspace_ptr), _vp(stream)))
 
 
 def variance_state_bytes(n_pixels):

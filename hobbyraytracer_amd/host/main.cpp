@@ -67,6 +67,15 @@
 //         --lens, --progressive, --aov*, --despeckle and --denoise; the previews of --progressive show the unnormalised sums over the
 //         samples done, and the feature buffers of --aov stay box-filtered)
 //     --filter-radius X (the filter's radius in pixels, 0.5 .. 2.5; tent 1, bspline 2, mitchell 2 by default; needs --filter)
+//     --bloom (the develop stage, DESIGN.md 4.17: the finished film -- after --despeckle and --denoise -- goes through hrt_develop on the
+//         first device before it is resolved; an energy-conserving pyramid bloom of 5 levels, mixed in at strength 0.05.  The image file and
+//         --dump-linear hold the developed film; previews, checkpoints and every --aov file stay undeveloped)
+//     --bloom-strength S (0 .. 1; 0.05)   --bloom-levels N (1 .. 8; 5)   (each implies --bloom)
+//     --exposure EV|auto (the same stage: EV, a number of stops from -64 to 64, multiplies the film by 2^EV; auto meters the film after
+//         the bloom -- the mean of its log luminance between the 10th and the 90th percentile -- and brings that level to 0.18)
+//     --exposure-key K (finite, > 0; 0.18)   --exposure-window LO,HI (0 <= LO < HI <= 1; 0.1,0.9)   (each implies --exposure auto and is
+//         a usage error with a numeric --exposure)
+//     --dump-undeveloped FILE.pfm (needs one of the develop flags: the linear film the stage received)
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -107,6 +116,10 @@ int main(int argc, char** argv) {
     std::string filterName;
     bool haveFilterRadius = false;
     double filter_s = 0.0;
+    bool develop = false, exposureNumeric = false, exposureAutoOnly = false;
+    std::string dumpUndeveloped;
+    hrt_develop_params dvp;
+    hrt_develop_defaults(&dvp);
     bool despeckle = false;
     hrt_despeckle_params dsp;
     hrt_despeckle_defaults(&dsp);
@@ -270,6 +283,47 @@ int main(int argc, char** argv) {
             despeckle = true; dsp.gate_z = x;
         }
         else if (a == "--despeckle-map") despeckleMap = next("--despeckle-map");
+        else if (a == "--bloom") { develop = true; if (dvp.bloom_levels == 0) dvp.bloom_levels = 5; }
+        else if (a == "--bloom-strength") {
+            const float x = number("--bloom-strength", next("--bloom-strength"));
+            if (!(x <= 1.0f)) { std::cerr << "--bloom-strength takes a number from 0 to 1" << std::endl; return 2; }
+            develop = true; dvp.bloom_strength = x;
+            if (dvp.bloom_levels == 0) dvp.bloom_levels = 5;
+        }
+        else if (a == "--bloom-levels") {
+            const char* v = next("--bloom-levels");
+            char* end = nullptr;
+            const long n = std::strtol(v, &end, 10);
+            if (end == v || *end != '\0' || n < 1 || n > 8) { std::cerr << "--bloom-levels takes an integer from 1 to 8" << std::endl; return 2; }
+            develop = true; dvp.bloom_levels = (int32_t)n;
+        }
+        else if (a == "--exposure") {
+            const std::string v = next("--exposure");
+            develop = true;
+            if (v == "auto") dvp.exposure_mode = 2;
+            else {
+                char* end = nullptr;
+                const double x = std::strtod(v.c_str(), &end);
+                if (end == v.c_str() || *end != '\0' || !std::isfinite(x) || std::fabs(x) > 64.0) { std::cerr << "--exposure takes auto or a number of stops from -64 to 64" << std::endl; return 2; }
+                dvp.exposure_mode = 1; dvp.exposure_ev = (float)x; exposureNumeric = true;
+            }
+        }
+        else if (a == "--exposure-key") {
+            const float x = number("--exposure-key", next("--exposure-key"));
+            if (!(x > 0.0f) || !std::isfinite(x)) { std::cerr << "--exposure-key takes a finite number > 0" << std::endl; return 2; }
+            develop = true; exposureAutoOnly = true; dvp.key = x;
+        }
+        else if (a == "--exposure-window") {
+            const char* v = next("--exposure-window");
+            char* end = nullptr;
+            const double lo = std::strtod(v, &end);
+            bool ok = end != v && *end == ',';
+            double hi = 0.0;
+            if (ok) { const char* v2 = end + 1; hi = std::strtod(v2, &end); ok = end != v2 && *end == '\0'; }
+            if (!ok || !(lo >= 0.0 && (float)lo < (float)hi && hi <= 1.0)) { std::cerr << "--exposure-window takes LO,HI with 0 <= LO < HI <= 1" << std::endl; return 2; }
+            develop = true; exposureAutoOnly = true; dvp.meter_low = (float)lo; dvp.meter_high = (float)hi;
+        }
+        else if (a == "--dump-undeveloped") dumpUndeveloped = next("--dump-undeveloped");
         else if (a == "--dump-variance") dumpVariance = next("--dump-variance");
         else if (a == "--dump-noisy") dumpNoisy = next("--dump-noisy");
         else if (!haveFile) { file = a; haveFile = true; }
@@ -291,6 +345,9 @@ int main(int argc, char** argv) {
     if (aovIds && aovPrefix.empty()) { std::cerr << (mattes.empty() ? "--aov-ids" : "--matte") << " needs --aov PREFIX" << std::endl; return 2; }
     if (!dumpNoisy.empty() && !denoise && !despeckle) { std::cerr << "--dump-noisy needs --denoise or --despeckle" << std::endl; return 2; }
     if (!despeckleMap.empty() && !despeckle) { std::cerr << "--despeckle-map needs --despeckle" << std::endl; return 2; }
+    if (exposureAutoOnly && exposureNumeric) { std::cerr << "--exposure-key and --exposure-window meter the film: they cannot be combined with a numeric --exposure" << std::endl; return 2; }
+    if (exposureAutoOnly) dvp.exposure_mode = 2;
+    if (!dumpUndeveloped.empty() && !develop) { std::cerr << "--dump-undeveloped needs --bloom or --exposure" << std::endl; return 2; }
     if (!dumpVariance.empty() && !measured) { std::cerr << "--dump-variance needs --denoise-variance measured" << std::endl; return 2; }
     if (!makeAssets.empty()) {
         long t = writeTeapotObj(makeAssets + "/teapot.obj", 1.0);
@@ -321,7 +378,8 @@ int main(int argc, char** argv) {
     if (opt.adaptive >= 0.0f && film->getFilm().samples < 2) { std::cerr << "--adaptive needs at least 2 samples per pixel" << std::endl; return 2; }
     if (haveAovSpp && aovSpp > film->getFilm().samples) { std::cerr << "--aov-spp must not exceed the samples per pixel (" << film->getFilm().samples << ")" << std::endl; return 2; }
     std::vector<float> aov;
-    double aov_s = 0.0, denoise_s = 0.0, variance_s = 0.0, despeckle_s = 0.0;
+    double aov_s = 0.0, denoise_s = 0.0, variance_s = 0.0, despeckle_s = 0.0, develop_s = 0.0;
+    hrt_develop_info developInfo{};
     unsigned long long despecklePixels = 0, despeckleRepaired = 0;
     std::vector<float> variance;
     if (measured || (despeckle && opt.adaptive >= 0.0f)) {   // (an adaptive render's buffers hold a variance: the outlier filter takes it)
@@ -390,6 +448,16 @@ int main(int argc, char** argv) {
             if (!writePFM(dumpVariance, img.data(), w, h)) { std::cerr << "cannot write " << dumpVariance << std::endl; return -1; }
         }
     }
+    if (develop) {   // the clean film through the develop stage on the first device, and resolved as the film resolves itself
+        const int w = film->getFilm().width, h = film->getFilm().height;
+        const auto t0 = std::chrono::high_resolution_clock::now();
+        const std::vector<float> undeveloped = film->linear();
+        st = hrt_develop(0, w, h, &dvp, undeveloped.data(), film->linear().data(), &developInfo, nullptr);
+        if (st == HRT_OK) st = hrt_denoise_resolve_u8(0, film->linear().data(), (int64_t)w * h, film->getPixels());
+        if (st != HRT_OK) { std::cerr << "develop: " << hrt_status_str(st) << ": " << hrt_last_error() << std::endl; return -1; }
+        develop_s = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
+        if (!dumpUndeveloped.empty() && !writePFM(dumpUndeveloped, undeveloped.data(), w, h)) { std::cerr << "cannot write " << dumpUndeveloped << std::endl; return -1; }
+    }
     int r = film->outputFilm();
     if (!dumpLinear.empty() && !writePFM(dumpLinear, film->linear().data(), film->getFilm().width, film->getFilm().height)) {
         std::cerr << "cannot write " << dumpLinear << std::endl;
@@ -457,7 +525,7 @@ int main(int argc, char** argv) {
                              12.0 * film->getFilm().width * film->getFilm().height;
         // wall_s: the reference's own stopwatch (main.cpp:144,184): process start to after the image file is written
         const double wall_s = std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - start).count();
-        char extra[512] = "";
+        char extra[1024] = "";
         if (opt.adaptive >= 0.0f) {   // the samples adaptive sampling took, and their share of the uniform render's
             const double uniform = (double)film->getFilm().width * film->getFilm().height * film->getFilm().samples;
             std::snprintf(extra, sizeof(extra), ", \"adaptive_threshold\": %g, \"samples_taken\": %llu, \"sample_fraction\": %.6f",
@@ -486,6 +554,11 @@ int main(int argc, char** argv) {
         if (opt.filter_kind >= 0) {   // the reconstruction filter: its kind and the time of its own kernels, from HIP events
             const size_t k = std::strlen(extra);
             std::snprintf(extra + k, sizeof(extra) - k, ", \"filter\": \"%s\", \"filter_s\": %.6f", filterName.c_str(), filter_s);
+        }
+        if (develop) {                // the develop stage and its resolve: the wall time, copies included; the levels used, the factor applied and,
+            const size_t k = std::strlen(extra);   // under --exposure auto, the metered level in stops (otherwise the stops given)
+            std::snprintf(extra + k, sizeof(extra) - k, ", \"develop_s\": %.6f, \"bloom_levels\": %u, \"exposure_scale\": %.9g, \"exposure_ev\": %.17g", develop_s,
+                          dvp.bloom_strength != 0.0f ? developInfo.levels : 0u, (double)developInfo.scale, dvp.exposure_mode == 2 ? developInfo.mean_ev : (double)dvp.exposure_ev);
         }
         if (measured) {               // the measured variance: the wall time of its folds on the first device, copies included
             const size_t k = std::strlen(extra);

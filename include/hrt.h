@@ -744,6 +744,91 @@ enum {
 hrt_status hrt_filter_samples(int device, int32_t kind, float radius, int32_t W, int32_t H, hrt_rect rect, uint32_t seed_lo, uint32_t seed_hi,
                               int32_t stratified, int32_t samples, const float* rad, float* out);
 
+/* ---- develop ----------------------------------------------
+ * The stage between the clean linear film and the resolve: an energy-conserving pyramid bloom, then an exposure -- none, a manual one
+ * in stops, or one metered from the film's own luminance histogram.  It needs no scene and does not touch the tone curve.  Everything
+ * is fp32 and uses only + - * / and comparisons, evaluated in the order written here without fused multiply-adds, so that a restatement
+ * of these words with IEEE fp32 operations gives the same bits (tests/develop_np.py); the two float64 passages are marked.
+ * Y(r, g, b) = 0.2126f * r + 0.7152f * g + 0.0722f * b, left to right.  clamp(v, a, b) = v < a ? a : v > b ? b : v.
+ *
+ * Input: rgb, the whole film in film order (row 0 = top), W x H pixels, 3 floats per pixel: the linear means c.
+ * A pixel is VALID when its three channels are finite.  An invalid pixel keeps its bits through the whole stage and contributes
+ * (0, 0, 0) to the pyramid.  Only whether an output is a NaN is defined, not a NaN's sign and payload.
+ *
+ * Bloom, with bloom_levels and bloom_strength s.  Level 0 is the film, W_0 x H_0 = W x H; level k + 1 is (W_k + 1) / 2 x (H_k + 1) / 2
+ * pixels (integer division), and levels exist while max(W_k, H_k) > 1: a 37 x 29 film has 6, a 1 x 1 film none.  L = min(bloom_levels,
+ * the levels that exist) is the effective level count.  With L = 0 or s = 0 the bloom is skipped: m = c, bit for bit.  Otherwise:
+ * 1. D_0(p) = c_p for a valid p, else (0, 0, 0).
+ * 2. Down, k = 0 .. L - 1, per channel:  D_{k+1}(x, y) is a sum that starts from +0.0f and adds the 16 taps in row-major order, j = 0 .. 3
+ *    outer, i = 0 .. 3 inner:  sum = sum + D_k(clamp(2x - 1 + i, 0, W_k - 1), clamp(2y - 1 + j, 0, H_k - 1)) * (w_j * w_i)  with
+ *    w = (0.125f, 0.375f, 0.375f, 0.125f); the weight products are exact in fp32.
+ * 3. Up, from a w x h level C to a finer size, per channel:  cx = x >> 1,  nx = clamp(cx + (x odd ? 1 : -1), 0, w - 1),  cy and ny
+ *    likewise from y and h,  U(C)(x, y) = C(cx, cy) * 0.5625f + C(nx, cy) * 0.1875f + C(cx, ny) * 0.1875f + C(nx, ny) * 0.0625f,
+ *    left to right.
+ * 4. E_L = D_L;  E_k = D_k + U(E_{k+1}) at level k's size, for k = L - 1 .. 1;  B = U(E_1) / (float)L at the film's size.
+ * 5. A valid p:  m_k = c_k * (1.0f - s) + B_k * s per channel, with 1.0f - s formed once.  An invalid p:  m = c, its bits.
+ * Both filters have weights that sum to 1, so B holds the film's sum, per channel, when everything lit lies at least 3 * 2^L pixels
+ * from every border (measured: within 1e-8 relative; the reach is 7 pixels at L = 2 and 19 at L = 3).  At the borders the clamped
+ * coordinates leak or gain a little (0.6 % on a 37 x 29 noise film): the stage does NOT preserve the film's sum there.
+ *
+ * Exposure, with exposure_mode:
+ *   0, none:    out = m, bit for bit.
+ *   1, manual:  scale = (float)exp2((double)exposure_ev), formed on the host;  out_k = m_k * scale for a valid p.
+ *   2, auto:    the film after bloom, m, is metered, and out_k = m_k * scale for a valid p:
+ *     A pixel is METERED when it is valid, l = Y(m) is finite and l >= meter_floor.  Its bin is b = bits(l) >> 20, 0 .. 2047: the
+ *     exponent and three mantissa bits, 8 bins to the stop, integer arithmetic only (0.18 -> 995, 1.0 -> 1016, 1.5 -> 1020).
+ *     n_b is the number of metered pixels of bin b, exact; N is their sum.  With N = 0:  scale = 1, mean_ev = 0.  Otherwise, in
+ *     float64, with C_b the number of metered pixels of the bins below b:
+ *       lo = (double)meter_low * N,  hi = (double)meter_high * N                      (the window, in pixels of the sorted film)
+ *       o_b = max(0, min(C_b + n_b, hi) - max(C_b, lo))                               (what of bin b lies inside the window)
+ *       ev_b = (double)((b >> 3) - 127) + c[b & 7],  c[k] = log2(1 + (k + 0.5) / 8):  (the bin's middle, in stops)
+ *         c = 0.0874628412503394, 0.2479275134435855, 0.3923174227787603, 0.5235619560570128,
+ *             0.6438561897747247, 0.7548875021634686, 0.8579809951275721, 0.9541963103868752
+ *       mean_ev = (sum of o_b * ev_b) / (sum of o_b), both over b ascending, then clamped to [ev_min, ev_max]
+ *       scale = (float)((double)key * exp2(-mean_ev))
+ *     The grouping of the two float64 sums and exp2 itself are not pinned: mean_ev is defined to 1e-9 and scale to one fp32 ulp, and
+ *     the film is m * (the scale the call reports), to the bit.
+ * An invalid pixel is never scaled.  The histogram is built in mode 2 only; in modes 0 and 1 every n_b and `metered` are 0, mean_ev is 0.
+ *
+ * Not part of it: a threshold or bright-pass, per-level tints, other tone curves, developing the previews of a
+ * progressive render, and the stage per stripe inside the multi-GPU session. */
+typedef struct hrt_develop_params {
+    int32_t bloom_levels;   /* 0 .. 8; default 0 = no bloom */
+    float bloom_strength;   /* [0, 1]; default 0.05: the share of the blurred film in the mix (a convention, not a measurement) */
+    int32_t exposure_mode;  /* 0 none, 1 manual, 2 auto; default 0 */
+    float exposure_ev;      /* finite, |ev| <= 64; default 0: manual exposure in stops */
+    float key;              /* finite, > 0; default 0.18: the luminance the metered level is brought to */
+    float meter_low;        /* 0 <= meter_low < meter_high <= 1; defaults 0.10 and 0.90: the window of the sorted metered pixels that ... */
+    float meter_high;       /* ... is averaged (the darkest and the brightest tenth are left out) */
+    float meter_floor;      /* finite, >= 2^-126; default 2^-16: luminances below it (black, negative) are not metered */
+    float ev_min;           /* finite; default -16 ... */
+    float ev_max;           /* ... finite, ev_min <= ev_max; default 16: the clamp of the metered level */
+} hrt_develop_params;
+typedef struct hrt_develop_info {
+    double mean_ev;         /* auto: the metered level in stops, after the clamp; otherwise 0 */
+    float scale;            /* what every valid pixel was multiplied by (1 in mode 0) */
+    uint32_t metered;       /* auto: N, the metered pixels; otherwise 0 */
+    uint32_t levels;        /* L, the effective level count (0: the bloom was skipped because there are no levels; s = 0 leaves L as it is) */
+    uint32_t pad;
+} hrt_develop_info;
+#define HRT_DEVELOP_BINS 2048
+/* Fills in the defaults, with which the stage is the identity. */
+void hrt_develop_defaults(hrt_develop_params* params);
+/* The bytes hrt_develop_device needs as workspace for a W x H film with bloom_levels = levels: the HRT_DEVELOP_BINS counters, the info
+ * record and the pyramid's levels 1 .. L (16 bytes per pixel of each); 0 when W or H is below 1, W x H above 2^30 or levels outside 0 .. 8. */
+uint64_t hrt_develop_workspace_bytes(int32_t W, int32_t H, int32_t levels);
+/* Asynchronous, on HIP stream `stream` of `device`: develops the DEVICE image d_rgb into d_out.  d_out == d_rgb is allowed (every launch
+ * that writes d_out reads its own pixel of d_rgb only); no other overlap is.  d_info (one hrt_develop_info) and d_hist
+ * (HRT_DEVELOP_BINS x uint32_t, the n_b) are optional DEVICE outputs and may be NULL.  d_workspace must be 16-byte aligned; the call clears
+ * its counters itself, in stream order, and two calls in flight need two workspaces.  HRT_ERR_INVALID, with a message, for a NULL
+ * required argument, W or H below 1, more than 2^30 pixels, a parameter outside its range or NaN, or a misaligned pointer -- decided
+ * before any device is touched, and the outputs are left untouched. */
+hrt_status hrt_develop_device(int device, int32_t W, int32_t H, const hrt_develop_params* params, const float* d_rgb, float* d_out,
+                              hrt_develop_info* d_info, uint32_t* d_hist, void* d_workspace, void* stream);
+/* Blocking, HOST buffers; out == rgb is allowed; info and hist may be NULL; allocates its own workspace on `device`.  The same refusals. */
+hrt_status hrt_develop(int device, int32_t W, int32_t H, const hrt_develop_params* params, const float* rgb, float* out,
+                       hrt_develop_info* info, uint32_t* hist);
+
 /* ---- multi-GPU session -----------------------------------
  * The reference's render() (main.cpp:81-140) has one parallel loop over all pixels of the film (main.cpp:111-135, no state
  * shared between pixels).  Here the flattened scene is replicated on `n_devices` GPUs of THIS process (`devices` = their
